@@ -10,12 +10,19 @@ copies of the results.  Weights are random-init (seed 0) of the named architectu
 captions never reach [SEP], so every frame pays the worst case of 16 decode steps and
 8 unique captions per video go through the filter.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (see README / DESIGN.md §measurement).  Beside the contract's fields it carries
-  roofline            dominant GEMM instantiation of one instrumented step (HIP events) against the 2.5 PFLOP/s MFMA peak
+A plain run sets up, runs the W warm-up steps (at least two: the first step of a shape runs the decode eagerly, the second
+captures its HIP graphs), times the K steps and prints the line.  --dump-outputs DIR writes what the last timed step returned
+(rank 0's videos) as float32 .npy files: the token ids of every video's candidate and kept captions and the class indices of
+its visual tokens.  --full adds, after the timed steps, everything else listed below.
+
+Rank 0 prints ONE JSON line (see README / DESIGN.md §measurement).  Beside the contract's fields every line carries
   config.algorithmic_gflop_per_frame / whole_path_mfma_frac      SURVEY §8d's algorithmic count (ITM captions at 35 tokens)
+  warmup_steps_run    the untimed steps that ran before the timed ones (`warmup` is the count asked for)
+and --full adds
+  roofline            dominant GEMM instantiation of one instrumented step (HIP events) against the 2.5 PFLOP/s MFMA peak
   config.executed_gflop_per_frame / executed_mfma_frac           what the launches of the instrumented step really computed
   secondary.streaming_input   the same step with FRESH frames every step, uploaded from pinned host memory on a copy stream under
                       the previous step (double-buffered), inside the timed region
@@ -343,6 +350,44 @@ def cpu_baseline(args, budget_s=240, parity_file=None):
                        f"{workers * t_per} of the host's {ncpu} hardware threads), oracle (PyTorch fp32) at the same time: reference "
                        f"schedule incl. {n_caps} ITM caption passes {dt:.1f} s (slowest worker); de-duplicated schedule (filter ViT "
                        f"once per frame, cross K/V once per image) {dt2:.1f} s")
+
+
+def dump_outputs(out_dir, items, toks, tok, onto_texts):
+    """What one step returns to its caller (``FramePipeline.process``: caption strings per video, visual-token strings per
+    frame), as float32 arrays, -1 = no entry: each caption as its token ids (the synthetic tokenizer round-trips ids
+    exactly), each visual token as the first index of its string in the category's class list."""
+    from vidil_amd.visual_tokenization import CATEGORIES
+
+    def caption_ids(key):
+        caps = [it[key] for it in items]
+        ids = [[tok.encode_one(c) for c in cs] for cs in caps]
+        L = max([len(x) for v in ids for x in v] or [1])
+        out = np.full((len(ids), max([len(v) for v in ids] or [1]), L), -1, np.float32)
+        for v, cs in enumerate(ids):
+            for c, x in enumerate(cs):
+                out[v, c, :len(x)] = x
+        return out
+
+    first = {key: {} for key in CATEGORIES}
+    for key in CATEGORIES:
+        for i, t in enumerate(onto_texts[key]):
+            first[key].setdefault(t, i)
+
+    def token_idx(per_cat, topk):
+        out = np.full((len(CATEGORIES), topk), -1, np.float32)
+        for c, key in enumerate(CATEGORIES):
+            for j, t in enumerate(per_cat[key]):
+                out[c, j] = first[key][t]
+        return out
+
+    vt = [toks[it["video_id"]] for it in items]
+    topk = max(len(ts) for v in vt for ft in v["frame_tokens"] for ts in ft.values())
+    arrays = {"captions_unfiltered": caption_ids("unfiltered_text"), "captions_kept": caption_ids("text"),
+              "visual_tokens_per_frame": np.stack([np.stack([token_idx(ft, topk) for ft in v["frame_tokens"]]) for v in vt]),
+              "visual_tokens_aggregated": np.stack([token_idx(v["aggregated_tokens"], topk) for v in vt])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def time_steps(step, n):
@@ -749,10 +794,16 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=CPU_WORKER_THREADS, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-sync-dir", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-parity-file", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary f16 / parity-mode / text-tower measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--gemm-shapes", action="store_true", help="developer: per-shape table of the instrumented step's GEMM launches on stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline step, the CPU baseline and the secondary measurements, and "
+                         "prime until two consecutive steps agree before the warm-up steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary f16 / parity-mode / text-tower measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full or --gemm-shapes: skip the instrumented roofline step")
+    ap.add_argument("--gemm-shapes", action="store_true",
+                    help="developer: per-shape table of the instrumented step's GEMM launches on stderr (runs the roofline step)")
     ap.add_argument("--itm-short-circuit", action="store_true",
                     help="secondary number: score a caption on the frame it came from first and on the other frames only if "
                          "it failed there (identical kept lists; the headline scores every pair like the reference)")
@@ -851,21 +902,25 @@ def main():
 
     log("models + inputs ready")
     # one-time initialisation, like weight packing: the first batch of a shape runs the decode steps eagerly, the
-    # second captures them into HIP graphs; steady state starts with the third (independent of --warmup)
-    # ... and a fresh box needs a few seconds of load before clocks and caches settle: keep priming (at most 8
-    # steps) until two consecutive steps agree within 2 %.
-    prev = None
-    for i in range(8):
-        torch.cuda.synchronize()
-        t_p = time.perf_counter()
-        step()
-        torch.cuda.synchronize()
-        t_p = time.perf_counter() - t_p
-        if i >= 2 and prev is not None and abs(t_p - prev) <= 0.02 * prev:
-            break
-        prev = t_p
-    log(f"sessions primed after {i + 1} steps (decode-step graphs captured, last step {t_p * 1e3:.1f} ms)")
-    for _ in range(args.warmup):
+    # second captures them into HIP graphs; steady state starts with the third
+    n_warmup = max(args.warmup, 2)               # a plain run primes inside its warm-up steps
+    if args.full:
+        # ... and a fresh box needs a few seconds of load before clocks and caches settle: keep priming (at most 8
+        # steps) until two consecutive steps agree within 2 %, then run the --warmup steps
+        prev = None
+        for i in range(8):
+            torch.cuda.synchronize()
+            t_p = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            t_p = time.perf_counter() - t_p
+            if i >= 2 and prev is not None and abs(t_p - prev) <= 0.02 * prev:
+                break
+            prev = t_p
+        log(f"sessions primed after {i + 1} steps (decode-step graphs captured, last step {t_p * 1e3:.1f} ms)")
+        n_warmup = args.warmup
+    n_untimed = n_warmup + (i + 1 if args.full else 0)
+    for _ in range(n_warmup):
         step()
         torch.cuda.synchronize()
         log("warmup step done")
@@ -882,6 +937,9 @@ def main():
     stats = dict(engine.last_stats)
     peak_gib = torch.cuda.max_memory_allocated() / 2**30
     log(f"timed region done: {dt:.3f}s for {args.steps} steps (peak device memory {peak_gib:.0f} GiB of 288 GB HBM3E)")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, items, toks, tok, onto_texts)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     result = None
     if rank == 0:
@@ -895,6 +953,7 @@ def main():
         result = {
             "metric": f"frames/sec whole-node (BLIP caption+filt + CLIP visual-token) {args.size}^2 8f/video",
             "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "warmup_steps_run": n_untimed,
             "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": args.dtype, "data": "synthetic, resident in HBM (same frames every step; H2D outside the timed region)",
             "config": {"workload": f"{Nv} synthetic videos x {F} frames {args.size}^2 per GPU per step (towers / ITM per {args.tower_chunk_videos or Nv} videos, one beam "
@@ -910,7 +969,7 @@ def main():
                        "whole_path_mfma_frac": round(fps / world * gflop_frame / 1e3 / MFMA_F16_PEAK_TFLOPS, 4),
                        "parallelism": f"dp{world} (videos sharded, no data-path collective)"},
         }
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and (args.full or args.gemm_shapes) and not args.no_roofline:
         timer = GemmTimer()
         timer.install()
         # (the instrumented step launches the decode steps one by one instead of replaying their graphs, so that
@@ -991,12 +1050,12 @@ def main():
                               "all_gemm": {k: {"launches": v[0], "tflops": round(v[1] / v[2] / 1e12, 1),
                                                "ms": round(v[2] * 1e3, 3)} for k, v in agg.items()}}
     parity_file = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log("cpu baseline...")
         import tempfile
         parity_file = os.path.join(tempfile.gettempdir(), f"vidil_bench_parity_{os.getpid()}.npz")
         result["cpu_baseline"] = cpu_baseline(args, parity_file=parity_file)
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         try:
             result.update(secondary_measurements(args, cap, flt, clip, step, frames, dev, parity_file, log, engine=engine, vtok=vtok,
                                                  onto_texts=onto_texts, clip_comp=clip_comp))
@@ -1040,7 +1099,7 @@ def main():
         result["statement"] = (f"value: {args.dtype} operands, plain precision mode — the throughput configuration (BASELINE configs[1]); the "
                                "parity statements ('caption logits within 1e-3' as an ABSOLUTE bound, also at a trained model's logit "
                                "scale; visual-token ranks equal to the reference form) hold in the configuration timed as "
-                               "`parity_qualified` (tests/test_trained_like_gpu.py, tests/test_parity_mode_gpu.py); every logit figure is on "
+                               "`parity_qualified` (a --full figure; tests/test_trained_like_gpu.py, tests/test_parity_mode_gpu.py); every logit figure is on "
                                "random-init or synthetic trained-like weights — no checkpoint can be mounted on the bench / test boxes, "
                                "tests/test_real_weights_gpu.py (3 tests) is skipped there")
         print(json.dumps(result), flush=True)

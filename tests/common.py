@@ -55,3 +55,20 @@ def synthetic_frames(n_videos, frames=8, size=224, first_video=0):
 from oracle.synth_weights import portable_init_, trained_like_  # noqa: E402,F401  (shared with bench.py's parity leg / smoke())
 
 
+
+
+FULLSIZE_SEED = 7
+FULLSIZE_PROMPT = [[30522, 1037, 3861, 1997]]
+
+
+def fullsize_captioner_state():
+    """Full-size captioner weights (ViT-B/16 @ 224 + decoder, portable_init_) and one frame, both from numpy seeds: the inputs
+    of tests/golden/fullsize_ref.npz (tests/golden/make_fullsize_golden.py)."""
+    from vidil_amd.blip import BLIP_Decoder
+    from vidil_amd.tokenizer import SyntheticBertTokenizer
+
+    cap = BLIP_Decoder(image_size=224, vit="base", tokenizer=SyntheticBertTokenizer())
+    portable_init_(cap, FULLSIZE_SEED)
+    sd = {k: v.detach().clone() for k, v in cap.state_dict().items()}
+    x = torch.from_numpy(np.random.default_rng(FULLSIZE_SEED).standard_normal((1, 3, 224, 224), dtype=np.float32))
+    return sd, x

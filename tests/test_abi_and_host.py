@@ -2,6 +2,7 @@
 include/vidil_hip.h declares (no compute calls), the ctypes mirror agrees with the header,
 argument validation fails loudly, and the host-side mirror of the reference interface."""
 import ctypes
+import json
 import os
 import re
 
@@ -174,13 +175,11 @@ def test_state_dict_names_match_reference_checkpoints():
     ik = set(itm.state_dict().keys())
     for k in ["itm_head.weight", "text_encoder.encoder.layer.3.crossattention.output.dense.weight", "vision_proj.weight"]:
         assert k in ik, k
-    if os.path.isfile("/root/reference/models/med.py"):
-        from oracle import ref_shim
-
-        _, med = ref_shim.load()
-        ref_keys = set("text_decoder." + k for k in med.BertLMHeadModel(ref_shim.med_config()).state_dict().keys())
-        mine = set(k for k in keys if k.startswith("text_decoder."))
-        assert ref_keys == mine, ref_keys ^ mine
+    # the reference's BertLMHeadModel(configs/med_config.json) key names (tests/golden/make_fullsize_golden.py)
+    with open(os.path.join(ROOT, "tests", "golden", "med_decoder_keys.json")) as f:
+        ref_keys = set("text_decoder." + k for k in json.load(f))
+    mine = set(k for k in keys if k.startswith("text_decoder."))
+    assert ref_keys == mine, ref_keys ^ mine
 
 
 def test_load_checkpoint_semantics(tmp_path):

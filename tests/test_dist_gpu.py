@@ -179,7 +179,7 @@ def test_bench_gpus_2_one_device_smoke(tmp_path):
     env = dict(os.environ, VIDIL_BENCH_SMOKE_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--videos-per-step", "16"]
+           "--videos-per-step", "16", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -203,7 +203,7 @@ def test_bench_launches_itself_for_gpus_1_and_gpus_2():
     One JSON line from rank 0, n_gpus = N, exit code 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    common = ["--steps", "1", "--warmup", "0", "--videos-per-step", "16", "--no-cpu-baseline", "--no-secondary"]
+    common = ["--steps", "1", "--warmup", "0", "--videos-per-step", "16"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common, env=env, cwd=ROOT,
                        capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])

@@ -1,15 +1,16 @@
 """CPU tests of the oracle: against the committed golden vectors (generated from the
-reference's own modules by tests/golden/make_golden.py) and, where /root/reference is
-present, against the reference modules run live."""
+reference's own modules by tests/golden/make_golden.py and, at full size and with the
+reference's ontology files, by tests/golden/make_fullsize_golden.py)."""
 import json
+import lzma
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from common import GOLDEN, load_golden
-from oracle import clip_ref, med_ref, ref_shim, tokens_ref, vit_ref
+from common import FULLSIZE_PROMPT, GOLDEN, fullsize_captioner_state, load_golden
+from oracle import clip_ref, med_ref, tokens_ref, vit_ref
 
 TOL = dict(rtol=1e-5, atol=2e-5)
 
@@ -93,34 +94,35 @@ def test_reference_shard_bounds_leave_ranks_empty():
     assert sizes == [3, 3, 3, 3, 3, 1, 0, 0]
 
 
-# --------------------------------------------------------------------- live reference (build container only)
-needs_ref = pytest.mark.skipif(not ref_shim.available(), reason="/root/reference not present")
+# --------------------------------------------------------------------- reference at full size, reference ontology files
+@pytest.fixture(scope="module")
+def ontology_root(tmp_path_factory):
+    """The reference's visual_token_ontology/ files the loaders read, written out from tests/golden/."""
+    root = tmp_path_factory.mktemp("visual_token_ontology")
+    with lzma.open(os.path.join(GOLDEN, "visual_token_ontology.json.xz"), "rt", encoding="utf-8") as f:
+        files = json.load(f)
+    for rel, text in files.items():
+        os.makedirs(os.path.join(root, os.path.dirname(rel)), exist_ok=True)
+        with open(os.path.join(root, rel), "w", encoding="utf-8") as f:
+            f.write(text)
+    return str(root)
 
 
-@needs_ref
 def test_oracle_vs_reference_full_size_modules():
-    vit_mod, med_mod = ref_shim.load()
-    torch.manual_seed(7)
-    v = vit_mod.VisionTransformer(img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12).eval()
-    x = torch.randn(1, 3, 224, 224)
-    sd = {"visual_encoder." + k: t for k, t in v.state_dict().items()}
+    """The reference's ViT-B/16 and BertLMHeadModel at full size (outputs in tests/golden/fullsize_ref.npz) against the
+    oracle on the same weights and frame (common.fullsize_captioner_state rebuilds both from numpy seeds)."""
+    g = np.load(os.path.join(GOLDEN, "fullsize_ref.npz"))
+    sd, x = fullsize_captioner_state()
+    y_ref = torch.from_numpy(g["y"])
     with torch.no_grad():
-        y, y2 = v(x), vit_ref.vit_forward(sd, x)
-    assert torch.allclose(y, y2, **TOL)
-    cfg = ref_shim.med_config()
-    dec = med_mod.BertLMHeadModel(cfg).eval()
-    dsd = {"text_decoder." + k: t for k, t in dec.state_dict().items()}
-    ids = torch.tensor([[30522, 1037, 3861, 1997]])
-    with torch.no_grad():
-        out = dec(ids, attention_mask=torch.ones_like(ids), encoder_hidden_states=y,
-                  encoder_attention_mask=torch.ones(1, 197, dtype=torch.long), return_dict=True, is_decoder=True)
-        lg, _ = med_ref.decoder_logits(dsd, ids, y)
-    assert torch.allclose(out.logits[:, -1], lg, **TOL)
+        y = vit_ref.vit_forward(sd, x)
+        lg, _ = med_ref.decoder_logits(sd, torch.tensor(FULLSIZE_PROMPT), y_ref)
+    assert torch.allclose(y, y_ref, **TOL)
+    assert torch.allclose(torch.from_numpy(g["logits"]), lg, **TOL)
 
 
-@needs_ref
-def test_ontology_filter_replayed_on_reference_files():
-    root = os.path.join(ref_shim.REFERENCE_ROOT, "visual_token_ontology")
+def test_ontology_filter_replayed_on_reference_files(ontology_root):
+    root = ontology_root
     from vidil_amd.visual_tokenization import load_visual_token_texts
 
     for name in ("vg", "vg_tencent"):
@@ -168,11 +170,10 @@ def test_deduplicated_cpu_schedule_gives_the_reference_schedule_results():
     assert all(np.array_equal(a, b) for a, b in zip(p_ref, p_dd))
 
 
-@needs_ref
-def test_youcook2_ontology_mapping_is_the_documented_one():
+def test_youcook2_ontology_mapping_is_the_documented_one(ontology_root):
     """Config 4 names a 'youcook2 ontology'; the reference ships the files but no loader branch (its YAML keeps 'vg').
     The build's mapping: cooking nouns -> objects, cooking verbs + relation triples -> verbs, vg attributes / scenes."""
-    root = os.path.join(ref_shim.REFERENCE_ROOT, "visual_token_ontology")
+    root = ontology_root
     from vidil_amd.visual_tokenization import OMIT_KEYWORDS, load_visual_token_texts
 
     yc = load_visual_token_texts(root, "youcook2")

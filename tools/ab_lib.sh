@@ -7,7 +7,7 @@ TAG=$1; shift
 R=$GRAFT_REPO_ROOT; cd /tmp; export TMPDIR=/tmp
 for L in "$@" "$1"; do
   if [ "$L" = tree ]; then unset VIDIL_HIP_LIB; else export VIDIL_HIP_LIB=$R/$L; fi
-  echo "== $L  (untraced, 3 steps)"; python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d.get('roofline'))"
+  echo "== $L  (untraced, 3 steps)"; python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d.get('roofline'))"
 done
 for L in "$@"; do
   if [ "$L" = tree ]; then unset VIDIL_HIP_LIB; else export VIDIL_HIP_LIB=$R/$L; fi

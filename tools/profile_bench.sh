@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 echo "$ARGS" > $OUT/cmdline.txt
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.log
+python $R/bench.py --full $ARGS > $OUT/bench.json 2> $OUT/bench.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python $R/bench.py $ARGS --no-roofline > $OUT/bench_traced.json 2>/dev/null
 python $R/tools/rocprof_summary.py $OUT/trace > $OUT/kernel_summary.md
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o f -- python $R/bench.py $ARGS --no-roofline > /dev/null 2>&1
