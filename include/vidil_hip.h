@@ -42,7 +42,7 @@ extern "C" {
  * precision mode of vidil_amd: caption logits within 1e-3 of the fp32 reference). */
 #define VIDIL_DT_SPLIT3 0x100
 /* with VIDIL_DT_SPLIT3 (vidil_layernorm; vidil_attention_f32's out_mode 3): rows laid out as three planes, but only planes
- * hi | lo are written — for a consumer that is a split_k GEMM in the K-loop form (vidil_gemm_split_k_in_loop), which reads
+ * hi | lo are written — for a consumer that is a split_k GEMM in the K-loop form (vidil_gemm_split_k_serves), which reads
  * planes 0 / 1 of its A rows only (ABI 10, round 5) */
 #define VIDIL_DT_SPLIT2 0x200
 
@@ -153,7 +153,7 @@ typedef struct vidil_gemm_args {
    * T16(v - hi)) of v = act(acc + bias) + resid — what vidil_split3_f32 would make of the f32 output, from the same f32
    * values — and `out` may then be NULL: the f32 rows are not written.  The parity precision mode's fc1 -> fc2 hand-over.
    * 2 = write planes hi | lo only (plane 2, a copy of plane 0, is left untouched): for a consumer that is a split_k launch in
-   * the K-loop form (vidil_gemm_split_k_in_loop() != 0 and an f32 / per-head (T >= 8) / patch epilogue), which reads planes 0 / 1. */
+   * the K-loop form (vidil_gemm_split_k_serves() == 1: an f32 / per-head (T >= 8) / patch epilogue), which reads planes 0 / 1. */
   int32_t out16_split3;
   /* ERROR-COMPENSATED operands (ABI 10, round 5; the parity precision mode): non-zero = A rows are [x_hi | x_lo | x_hi]
    * (three planes of Kl = K / 3 columns: what VIDIL_DT_SPLIT3 outputs look like) and W rows are [W_hi | W_hi | W_lo], so
@@ -173,13 +173,10 @@ typedef struct vidil_gemm_args {
  * 236,301,314,512,534; timm PatchEmbed conv (models/vit.py:144-145,182) as an
  * im2col-free GEMM; HF CLIP q/k/v/out/fc1/fc2/projection Linears. */
 int vidil_gemm(const vidil_gemm_args* args, void* stream);
-/* 1 when split_k launches with an eligible epilogue take the K-loop form in this process (0: $VIDIL_GEMM_C3=0 — every split_k
- * launch is the plain K = 3 Kl product and reads all three planes of its A rows). */
-int vidil_gemm_split_k_in_loop(void);
 /* (ABI 12) Per CALL: 1 when vidil_gemm would run `args` (split_k != 0) in the K-loop form — planes 0 / 1 of the A rows are
  * all it reads, so their producer may be run with VIDIL_DT_SPLIT2 / out16_split3 = 2 / out_mode 3 —, 0 when it would run the plain
  * K = 3 Kl product over all three planes (split_k == 2 is then refused by vidil_gemm), < 0 for invalid arguments.  Launches
- * nothing.  Hosts size their producers' `planes` with it instead of assuming vidil_gemm_split_k_in_loop() covers every call. */
+ * nothing.  Hosts size their producers' `planes` with it, per call. */
 int vidil_gemm_split_k_serves(const vidil_gemm_args* args);
 /* Name of the kernel instantiation vidil_gemm would launch for `args` (the spelling rocprofv3 prints, e.g.
  * "gemm256_kernel<f16, 1, 0>"), written NUL-terminated into buf[0..n).  For profilers / bench.py. */

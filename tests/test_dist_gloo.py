@@ -31,7 +31,7 @@ assert vdist.ranks_seen() == world, vdist.ranks_seen()          # one identity p
 # the collective of gather_json is chosen before it is issued: both forms deliver the same list to rank 0, None elsewhere
 assert vdist._gather_supported()
 a = vdist.gather_json(dict(rank=rank))
-os.environ["VIDIL_GATHER"] = "allgather"
+vdist._GATHER_BACKENDS = ()          # (as for a backend without gather)
 assert not vdist._gather_supported()
 b = vdist.gather_json(dict(rank=rank))
 assert a == b == ([dict(rank=r) for r in range(world)] if rank == 0 else None), (a, b)
@@ -69,7 +69,7 @@ def _run(world, out):
         print("rendezvous failure, retrying on a new port:\n" + "\n".join(bad), file=sys.stderr)
 
 
-def test_two_rank_gather_equals_single_process(tmp_path):
+def test_two_rank_gather_in_both_collective_forms_equals_single_process(tmp_path):
     out1, out2 = str(tmp_path / "w1"), str(tmp_path / "w2")
     _run(1, out1)
     _run(2, out2)

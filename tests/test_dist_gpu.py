@@ -132,7 +132,7 @@ assert vdist._comm_device().type == "cuda"
 assert vdist.gather_json({"a": [1, 2, 3]}) == [{"a": [1, 2, 3]}]
 assert vdist.max_over_ranks(1.25) == 1.25
 assert vdist.ranks_seen() == 1          # (round 6: the device identity — GPU UUID — all_gather'ed as a DEVICE buffer over RCCL)
-os.environ["VIDIL_GATHER"] = "allgather"
+vdist._GATHER_BACKENDS = ()          # (as for a backend without gather)
 assert vdist.gather_json({"b": 2}) == [{"b": 2}]          # (the other collective form, chosen before it is issued)
 vdist.barrier()
 print("nccl-single-rank-ok")

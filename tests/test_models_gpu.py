@@ -409,8 +409,7 @@ def test_itm_with_layernorms_folded_into_the_text_stack_vs_oracle_and_vs_the_unf
     pair_text = torch.arange(len(caps)).repeat(F)
     out = {}
     for mode, env in (("fused", {}), ("unfused", {"VIDIL_FUSE_LN": "0"})):
-        for k_ in ("VIDIL_FUSE_LN_MIN_ROWS", "VIDIL_FUSE_LN"):
-            monkeypatch.delenv(k_, raising=False)
+        monkeypatch.delenv("VIDIL_FUSE_LN", raising=False)
         for k_, v_ in env.items():
             monkeypatch.setenv(k_, v_)
         a = itm.itm_pairs(y16, F, ids, lens, torch.arange(F, dtype=torch.int32)).cpu()

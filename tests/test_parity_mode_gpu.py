@@ -745,7 +745,7 @@ def test_parity_qualified_results_do_not_depend_on_batch_composition():
         assert t[f"video{v}"] == all_t[f"video{v}"]
 
 
-def test_split_k_two_plane_operands_are_refused_where_the_plain_product_would_read_the_third_plane():
+def test_split_k_two_plane_operands_are_refused_where_the_call_runs_the_plain_product():
     """producers leave plane 2 of their [hi | lo | hi] rows unwritten only where the CONSUMER call takes the
     K-loop form — asked per call (vidil_gemm_split_k_serves) — and a consumer told its A rows hold two planes (split_k = 2) fails
     with EINVAL instead of running the plain K = 3 Kl product over the unwritten plane.  The per-head epilogue with fewer than 8
@@ -765,7 +765,6 @@ def test_split_k_two_plane_operands_are_refused_where_the_plain_product_would_re
     v = torch.zeros((B, H, T, 64), dtype=torch.float16, device=DEV)
     heads = dict(k=k, vt=v, T=T, H=H, part0=1, t_off=0, Tk_cap=T, NP=0)
     out32 = torch.empty((M, 2 * C), dtype=torch.float32, device=DEV)
-    assert K.split_k_in_loop()
     assert K.split_k_serves(a3, w3_, bias, out=out32)                  # f32 epilogue: the K-loop form at every size
     assert not K.split_k_serves(a3, w3_, bias, heads=heads)            # 5 tokens per sequence: the plain K = 3 Kl product
     # three valid planes: served by the plain product, same values as the f32 epilogue's

@@ -1,7 +1,7 @@
 """Developer experiment (round 5): the WEIGHT-ABSORBED form of the decode steps' cross-attention, priced with
 measurements before any kernel is written.
 
-Today (per decoder layer and decode step, 3,584 images x 3 beams): attn_direct_kernel streams every image's K | V fragment tiles
+Today (per decoder layer and decode step, 3,584 images x 3 beams): the direct kernel streams every image's K | V fragment tiles
 (2 x 197 x 768 x 2 B = 605 KB per image) once: 2.2 GB per launch.  The absorbed form scores against the ENCODER STATES, which are the
 same for all 12 layers: s = (q_h W_k,h) . enc^T, o_h = (P . enc) W_v,h^T (+ b_v; q . b_k is softmax-invariant) — 302 KB per image
 instead of 605, and no cross K | V projection (5.58 GFLOP per frame, ~20 ms per step).  What it adds:
@@ -43,7 +43,7 @@ vt = torch.randn(B, H, Tc, 64, generator=g).bfloat16().to(dev)
 q16 = (torch.randn(R, H, 1, 64, generator=g) * 0.125).bfloat16().to(dev)
 o16 = torch.zeros(R, C, dtype=torch.bfloat16, device=dev)
 t_now = timeit(lambda: K.attention(q16, kt, vt, o16, Bq=R, H=H, Nq=1, Nk=T, Tq_cap=1, Tk_cap=Tc, NP=Tc, kv_group=nb, kv_tiled=True))
-print(f"today: attn_direct_kernel on K | V tiles           {t_now:7.1f} us per launch  (2.20 GB -> {2.2e9 / t_now / 1e6:.2f} TB/s)")
+print(f"today: the direct kernel on K | V tiles      {t_now:7.1f} us per launch  (2.20 GB -> {2.2e9 / t_now / 1e6:.2f} TB/s)")
 del kt, vt
 # the byte side of the absorbed form: enc read once per launch (1.08 GB) + q~ read + c written (198 MB each)
 enc = torch.randn(B, T, C, generator=g).bfloat16().to(dev)

@@ -219,7 +219,7 @@ class BLIP_Decoder(nn.Module):
         own HIP streams (``_beam_search`` is a generator that yields after queueing each step; the parts are stepped
         round robin).  Measured at 3,072 images: 2 parts +0.2 %, 3 parts -1.4 %, 4 parts -3.8 % of the whole step — the
         ~160 launches of a decode step are short but each already covers the chip (decode time scales ~1/CUs under a
-        CU mask, tools/exp_cu_mask.py), so the default stays 1; kept for small batches per part of a larger job.
+        CU mask), so the default stays 1; kept for small batches per part of a larger job.
         A search is per image, so the tokens do not depend on the split.
 
         ``repetition_penalty`` != 1.0 (models/blip.py:127,161; the captioning call site leaves it at 1.0): the candidate

@@ -188,16 +188,12 @@ def _run_layers(layers, x, B, T, H, eps, *, causal=False, kv_len=None, f32_attn=
         #  the consumers state a_planes so that a launch that would read an unwritten plane fails instead)
         qkv32 = torch.empty((M, 3 * D), dtype=torch.float32, device=dev) if f32_attn else None
         planes, l0 = 3, layers[0]
-        if K.split_k_in_loop():
-            qkv_kw = dict(out=qkv32) if f32_attn else dict(heads=heads)
-            if (K.split_k_serves(a3, l0["qkv_w3"], l0["qkv_b"], **qkv_kw) and K.split_k_serves(o3, l0["o_w3"], l0["o_b"], out=x, resid=x)
-                    and K.split_k_serves(a3, l0["fc1_w3"], l0["fc1_b"], split3_out=hid3, act=K.ACT_QUICK_GELU)
-                    and K.split_k_serves(hid3, l0["fc2_w3"], l0["fc2_b"], out=x, resid=x)):
-                planes = 2
-        import os
-        if planes == 2 and os.environ.get("VIDIL_POISON_SPLIT3") == "1":       # (developer: NaNs in the unwritten third planes —
-            for _b in (a3, o3, hid3,):                               #  any consumer that reads one shows up at once)
-                _b[:, 2 * (_b.shape[1] // 3):] = float("nan")
+        qkv_kw = dict(out=qkv32) if f32_attn else dict(heads=heads)
+        if (K.split_k_serves(a3, l0["qkv_w3"], l0["qkv_b"], **qkv_kw) and K.split_k_serves(o3, l0["o_w3"], l0["o_b"], out=x, resid=x)
+                and K.split_k_serves(a3, l0["fc1_w3"], l0["fc1_b"], split3_out=hid3, act=K.ACT_QUICK_GELU)
+                and K.split_k_serves(hid3, l0["fc2_w3"], l0["fc2_b"], out=x, resid=x)):
+            planes = 2
+        K.poison_third_plane(planes, a3, o3, hid3)
         cls_last = cls_last and f32_attn and not causal and kv_len is None and T > 1
         for li, l in enumerate(layers):
             K.layernorm(x, l["n1g"], l["n1b"], eps, out16=a3, split3=True, planes=planes)

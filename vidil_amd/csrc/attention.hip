@@ -22,10 +22,6 @@
 //                      from HBM/L2 into MFMA operands (no LDS round trip); ONE wave
 //                      owns a (batch, head) unit and walks its key tiles, the next
 //                      tile requested before the current one is computed.
-//   attn_direct_kernel the same with the 4 waves of a workgroup splitting a unit's
-//                      key tiles (flash-decoding) and merging (m, l, O) through LDS:
-//                      the form before the end of round 5, kept behind
-//                      $VIDIL_ATTN_DIRECT1=0 for A / B measurements.
 // (plus the streamed tower kernel, the one-tile wave kernel and, further down, the
 //  f32 / split-operand kernels of the parity precision mode: each has its own header)
 //
@@ -909,217 +905,20 @@ __global__ __launch_bounds__(512, 4) void attn_stream_kernel(const AttnP<T> p) {
 #endif
 }
 
-// ------------------------------------------------------------------ direct (no K/V staging) kernel
-// rows <= 32.  4 waves; wave w handles key tiles w, w+4, ...; partials merged by wave 0.
+// ------------------------------------------------------------------ direct kernel, ONE WAVE per (kv batch, head)
+// rows <= 32, K / V in fragment tiles or in rows (any number of key tiles): every K / V element is used by one wave only, so the
+// fragments are loaded straight from HBM / L2 into MFMA operands.  It replaced a four-wave kernel that split a unit's key tiles
+// over its waves and merged the partials through LDS — measured (round 5, 3,584 images x 12 heads x 197 keys, developer
+// ablation): the loads alone 355 us (6.1 TB/s), with the merge 371, with the arithmetic 455 (plain) / 551 (split Q and P).  Here a
+// wave owns a whole unit: it walks the unit's key tiles with the online softmax, tile kt + D requested before tile kt is computed
+// (a register ring of D + 1 fragment sets), so every resident wave has D tiles (8 KiB each) in flight at any time; no LDS, no
+// barrier, no merge — the 32 rows leave straight from the accumulators.  Every launch of <= 32 rows and more than one key tile
+// comes here, in either K / V layout (a session's tiled and row-major forms give the same bits).
 // QS (split-operand form, the parity precision mode's decode cross-attention): f32 queries split into hi + lo in the kernel and
 // the probabilities split alike — S = K.Q_lo + K.Q_hi, O += V.P_lo + V.P_hi — against the SAME 16-bit K / V tiles.  Which of the
 // four operands need more than 16 bits was measured on the CPU oracle (tests/probes/probe_precision_design.py, trained-like
 // statistics, of the logit scale): Q 1.7e-4, P 6.3e-5, V 2.1e-5, K 1.0e-5 — with Q and P split the 16-bit K / V leave 3.0e-5 where
 // the budget of "1e-3 absolute" at max|logit| = 16 is 6.4e-5, at the byte traffic of the plain kernel (f32 K / V: twice the bytes).
-template <typename T, int NKT, bool QS = false, int VAR = 0>   // VAR 2 (the QS form at 197 keys): three waves per SIMD, one key tile per wave and round
-__global__ __launch_bounds__(256, VAR ? 3 : 1) void attn_direct_kernel(const AttnP<T> p) {
-  using f16 = T;
-  using f16x8 = typename Elt<T>::x8;
-  __shared__ float part_m[4][32];
-  __shared__ float part_l[4][32];
-  __shared__ float part_o[4][64][33];  // [wave][d][row] (+1 pad)
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hi = lane >> 5, l31 = lane & 31;
-  const int h = blockIdx.y;
-  int bk, first, count;
-  resolve_unit(p, blockIdx.z, bk, first, count);
-  const int rows = count * p.Nq;
-  if (rows <= 0) return;  // uniform: a kv batch nobody attends to
-  const int nk = p.Nk;
-  const RowInfo ri = row_info(p, l31, first, rows);
-
-  float m = -INFINITY, l = 0.f;
-  f32x16 O[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) O[dt][r] = 0.f;
-
-  const f16* kg = p.k + ((size_t)bk * p.H + h) * p.Tk_cap * 64;
-  const f16* vg = p.vt + ((size_t)bk * p.H + h) * 64 * (size_t)(p.tiled ? p.Tk_cap : p.NP);
-  const int ntiles = (nk + 31) >> 5;
-  if (wave < ntiles) {
-    f16x8 qf[4], ql[QS ? 4 : 1];
-    if constexpr (QS) {
-      const float* qg = p.q32 + ((size_t)ri.qb * p.Nq + ri.t) * p.ldq32 + h * 64 + hi * 8;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const f32x4 a = *(const f32x4*)(qg + ks * 16) * p.q_scale, b = *(const f32x4*)(qg + ks * 16 + 4) * p.q_scale;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          qf[ks][e] = Elt<T>::from_f32(a[e]);
-          ql[ks][e] = Elt<T>::from_f32(a[e] - (float)qf[ks][e]);
-          qf[ks][4 + e] = Elt<T>::from_f32(b[e]);
-          ql[ks][4 + e] = Elt<T>::from_f32(b[e] - (float)qf[ks][4 + e]);
-        }
-      }
-    } else {
-      const f16* qg = p.q + (((size_t)ri.qb * p.H + h) * p.Tq_cap + ri.t) * 64 + hi * 8;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const f16x8*)(qg + ks * 16);
-    }
-    int kmin = ri.klim;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int x = __shfl_xor(kmin, o, 64);
-      kmin = x < kmin ? x : kmin;
-    }
-    // This kernel streams each K / V^T byte exactly once and is HBM-bound, so every load of the wave's (up
-    // to NI) key tiles is issued before the first MFMA: 16 x 16 B per lane in flight instead of 4.
-    // Sequences longer than 8 key tiles (577 image tokens at 384^2) go through rounds of 2 tiles per wave.
-    constexpr int NI = VAR == 2 ? 1 : (NKT >= 8 ? 2 : (NKT + 3) / 4);
-    constexpr int ROUNDS = (NKT + 4 * NI - 1) / (4 * NI);
-#pragma unroll 1
-    for (int round = 0; round < ROUNDS; ++round) {
-    const int kt0 = round * 4 * NI + wave;
-    if (kt0 >= ntiles) break;
-    f16x8 kf[NI][4], vf[NI][2][2];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int kt = kt0 + 4 * i;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) kf[i][ks] = zero8<T>();
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb) vf[i][dt][hb] = zero8<T>();
-      if (kt < ntiles && p.tiled) {
-        // fragment tiles: each instruction of the wave reads one contiguous KiB; rows / key groups past the
-        // last key are not fetched (they stay zero and are masked below)
-        const f16* kt_base = kg + (size_t)kt * 2048 + (hi * 32 + l31) * 8;
-        if (kt * 32 + l31 < nk) {
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) kf[i][ks] = *(const f16x8*)(kt_base + ks * 512);
-        }
-        const f16* vt_base = vg + (size_t)kt * 2048 + (hi * 32 + l31) * 8;
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb) {
-          if ((kt * 2 + hb) * 16 + 4 * hi < nk) {
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) vf[i][dt][hb] = *(const f16x8*)(vt_base + (hb * 2 + dt) * 512);
-          }
-        }
-      } else if (kt < ntiles) {
-        int krow = kt * 32 + l31;
-        krow = krow < nk ? krow : nk - 1;  // clamped rows are masked below
-        const f16* kr = kg + (size_t)krow * 64 + hi * 8;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) kf[i][ks] = *(const f16x8*)(kr + ks * 16);
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb) {
-          // this half-wave's 8 keys of the 16-key block are 16 contiguous bytes (vt_pos order)
-          const int blk0 = (kt * 2 + hb) * 16;
-          if (blk0 < nk) {
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) vf[i][dt][hb] = *(const f16x8*)(vg + (size_t)(dt * 32 + l31) * p.NP + blk0 + 8 * hi);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int kt = kt0 + 4 * i;
-      if (kt >= ntiles) break;
-      f32x16 S;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) S[r] = 0.f;
-      if constexpr (QS) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) S = Elt<T>::mfma32(kf[i][ks], ql[ks], S);
-      }
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) S = Elt<T>::mfma32(kf[i][ks], qf[ks], S);
-      const bool tail = (kt * 32 + 32) > nk;  // tile reaches past the last key: V^T needs zeroing too
-      const bool need_mask = (kt * 32 + 32) > kmin;
-      auto vfrag = [&](int dt, int hb) {
-        const int blk0 = (kt * 2 + hb) * 16;
-        f16x8 v = vf[i][dt][hb];
-        if (tail) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            if (blk0 + 4 * hi + (e & 3) + 8 * (e >> 2) >= nk) v[e] = (f16)0.f;
-        }
-        return v;
-      };
-      // (a wave's first tile, known at compile time when one round covers the keys: nothing to rescale)
-      if constexpr (QS) softmax_pv_tile_psplit<T>(S, kt * 32, ri.klim, need_mask, m, l, O, vfrag);
-      else if (ROUNDS == 1 && i == 0) softmax_pv_tile<T, true, false, true>(S, kt * 32, ri.klim, need_mask, m, l, O, vfrag);
-      else softmax_pv_tile<T, true, false>(S, kt * 32, ri.klim, need_mask, m, l, O, vfrag);
-    }
-    }  // rounds
-  }
-  // ---- merge the waves' partials --------------------------------------------------------------
-  l += __shfl_xor(l, 32, 64);
-  if (hi == 0) { part_m[wave][l31] = m; part_l[wave][l31] = l; }
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) part_o[wave][dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi][l31] = O[dt][r];
-  __syncthreads();
-  // all 256 threads: thread = (row = tid&31, d-block = tid>>5 of 8 d values)
-  {
-    const int row = tid & 31, db = tid >> 5;
-    if (row < rows) {
-      float mm = part_m[0][row];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) mm = fmaxf(mm, part_m[w][row]);
-      float sc[4], lt = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        sc[w] = part_m[w][row] == -INFINITY ? 0.f : __expf(part_m[w][row] - mm);
-        lt += part_l[w][row] * sc[w];
-      }
-      const float inv = lt > 0.f ? 1.0f / lt : 0.f;
-      const int g = row / p.Nq;
-      const int qb = first + g, t = row - g * p.Nq;
-      f16x8 o8, l8, h8;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int d = db * 8 + e;
-        float acc = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) acc += part_o[w][d][row] * sc[w];
-        const float x = acc * inv;
-        o8[e] = (f16)x;             // (plain rows: the compiler may fold the multiply into the conversion — one rounding)
-        // [hi | lo | hi]: hi and the value lo is taken against MUST be the same conversion of the same f32 — with the fold
-        // above hi was RN16(acc . inv) while lo was computed against RN16(RN32(acc . inv)): one element in ~10^4 sits between
-        // the two, and its hi + lo was one f16 ulp off (round 5: tests/test_parity_mode_gpu.py, split form on fragment tiles)
-        const f16 h16 = Elt<T>::from_f32(x);
-        h8[e] = h16;
-        l8[e] = Elt<T>::from_f32(x - (float)h16);
-      }
-      f16* const og = p.out + ((size_t)qb * p.Nq + t) * p.ldo + h * 64 + db * 8;
-      if (p.out_mode >= 2) {       // [hi | lo | hi] planes (VIDIL_DT_SPLIT3; 3: hi | lo only)
-        const int pl = p.ldo / 3;
-        *(f16x8*)og = h8;
-        *(f16x8*)(og + pl) = l8;
-        if (p.out_mode == 2) *(f16x8*)(og + 2 * pl) = h8;
-      } else {
-        *(f16x8*)og = o8;
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------ direct kernel, ONE WAVE per (kv batch, head)
-// rows <= 32, K / V in fragment tiles or in rows (any number of key tiles).  The four-wave kernel above splits a unit's key tiles over its
-// waves, issues every load, computes, and merges the partials through LDS: nothing of a workgroup is in flight while it computes
-// and merges, and the overlap has to come from the other workgroups of the CU — measured (round 5, 3,584 images x 12 heads x 197
-// keys, developer ablation): the loads alone 355 us (6.1 TB/s), with the merge 371, with the arithmetic 455 (plain) / 551 (split
-// Q and P).  Here a wave owns a whole unit: it walks the unit's key tiles with the online softmax, tile kt + D requested before
-// tile kt is computed (a register ring of D + 1 fragment sets), so every resident wave has D tiles (8 KiB each) in flight at any
-// time; no LDS, no barrier, no merge — the 32 rows leave straight from the accumulators.  QS: the split form (f32 queries and the
-// probabilities as hi + lo, as above).  The summation order differs from the four-wave kernel's (one running (m, l, O) instead of
-// four merged ones), so a shape takes ONE of the two at every batch size and in either K / V layout: every launch of <= 32 rows and
-// more than one key tile comes here (a session's tiled and row-major forms give the same bits, as they did on the four-wave kernel).
 template <typename T, bool QS, int D, bool TILED>
 __global__ __launch_bounds__(256, (QS || !TILED) ? 2 : 3) void attn_direct1_kernel(const AttnP<T> p) {
   using f16 = T;
@@ -1372,27 +1171,13 @@ int launch_stream(const AttnP<T>& p, hipStream_t s) {
   return VIDIL_OK;
 }
 
-// the one-wave-per-unit direct kernel; $VIDIL_ATTN_DIRECT1=0 keeps the four-wave kernel (developer A / B)
-template <typename T>
-bool direct1_enabled(const AttnP<T>& p) {
-  const char* e = vidil_dev_env("VIDIL_ATTN_DIRECT1");
-  return e == nullptr || e[0] != '0';
-}
 template <typename T, bool QS>
 int launch_direct1(const AttnP<T>& p, hipStream_t s) {
   VIDIL_REQUIRE((long long)p.H * p.n_kv < 0x7fffffffLL, "attention: H=%d x %d kv batches overflow the unit index", p.H, p.n_kv);
   const int units = p.H * p.n_kv;
   const dim3 grid((units + 3) / 4);
   // prefetch depth (round 5, 3,584 images x 12 heads x 197 keys): plain 370 us at depth 1 (depth 2 spills: 588), split 402 at depth 1,
-  // 413 at 2 ($VIDIL_ATTN_DIRECT1_DEPTH=2, split form only); the four-wave kernel 461 / 544
-  if constexpr (QS) {
-    const char* e = vidil_dev_env("VIDIL_ATTN_DIRECT1_DEPTH");
-    if (e != nullptr && atoi(e) == 2 && p.tiled) {
-      hipLaunchKernelGGL((attn_direct1_kernel<T, true, 2, true>), grid, dim3(256), 0, s, p);
-      VIDIL_CHECK_LAUNCH("attention/direct1");
-      return VIDIL_OK;
-    }
-  }
+  // 413 at 2; the four-wave kernel it replaced 461 / 544
   if (p.tiled) hipLaunchKernelGGL((attn_direct1_kernel<T, QS, 1, true>), grid, dim3(256), 0, s, p);
   else hipLaunchKernelGGL((attn_direct1_kernel<T, QS, 1, false>), grid, dim3(256), 0, s, p);
   VIDIL_CHECK_LAUNCH("attention/direct1");
@@ -1408,12 +1193,7 @@ int launch_any(const AttnP<T>& p, int max_rows, hipStream_t s) {
     VIDIL_CHECK_LAUNCH("attention/wave");
     return VIDIL_OK;
   }
-  if (max_rows <= 32) {
-    if (direct1_enabled(p)) return launch_direct1<T, false>(p, s);
-    hipLaunchKernelGGL((attn_direct_kernel<T, NKT>), dim3(1, p.H, p.n_kv), dim3(256), 0, s, p);
-    VIDIL_CHECK_LAUNCH("attention/direct");
-    return VIDIL_OK;
-  }
+  if (max_rows <= 32) return launch_direct1<T, false>(p, s);
   if (max_rows > 128) return launch_lds<T, NKT, 8>(p, max_rows, s);
   return launch_lds<T, NKT, 4>(p, max_rows, s);
 }
@@ -1435,12 +1215,7 @@ int attention_dispatch(const AttnP<T>& p, int nkt, int max_rows, int Nk, hipStre
   // longer sequences (577 tokens of a 384^2 ViT-B/16, 257+ of others): rounds of key tiles in the direct
   // kernel, 224-key chunks re-staged through LDS in the staged kernel
   if (nkt <= 24) {
-    if (max_rows <= 32) {
-      if (direct1_enabled(p)) return launch_direct1<T, false>(p, s);
-      hipLaunchKernelGGL((attn_direct_kernel<T, 24>), dim3(1, p.H, p.n_kv), dim3(256), 0, s, p);
-      VIDIL_CHECK_LAUNCH("attention/direct");
-      return VIDIL_OK;
-    }
+    if (max_rows <= 32) return launch_direct1<T, false>(p, s);
     if (max_rows > 128) return launch_lds<T, 7, 8>(p, max_rows, s);
     return launch_lds<T, 7, 4>(p, max_rows, s);
   }
@@ -1824,11 +1599,8 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
 // MFMAs): K in the GEMMs' XOR-swizzled 128-byte rows (ds_read_b128 fragments), V row-major in [d / 16][32 keys][16 d] blocks
 // that ds_read_b64_tr_b16 reads transposed (the streamed tower kernel's layout: no key permutation, no 2-byte scatter).
 // 24 MFMAs of v_mfma_f32_32x32x16 per 32 x 32 tile where the f32-input form issues 64 instructions of twice the latency.
-template <typename T16, int NW>      // NW waves = NW x 32 virtual query rows of a unit per workgroup (8: a tower's 197 rows in ONE workgroup,
-#ifndef VIDIL_SPLIT_LB8
-#define VIDIL_SPLIT_LB8 4
-#endif
-__global__ __launch_bounds__(NW * 64, NW == 8 ? VIDIL_SPLIT_LB8 : 3) void attn_split_kernel(const AttnF32P p) {   // its K / V staged once)
+template <typename T16, int NW>      // NW waves = NW x 32 virtual query rows of a unit per workgroup (launched with NW = 4)
+__global__ __launch_bounds__(NW * 64, 3) void attn_split_kernel(const AttnF32P p) {
   using x8 = typename Elt<T16>::x8;
   using x4 = typename Elt<T16>::x4;
   typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -2149,9 +1921,7 @@ extern "C" int vidil_attention_f32(const vidil_attn_f32_args* a, void* stream) {
   if (a->anc != nullptr) {
     VIDIL_REQUIRE(a->Nq == 1 && a->arena_rows > 0 && a->anc_ld >= a->Nk, "attention_f32: the arena form serves one query row per batch");
     const int units = a->Bq * a->H;
-    const char* eg = vidil_dev_env("VIDIL_ATTN_F32_ARENA_GATHER");       // (developer: 0 = the one-key-at-a-time kernel)
-    const bool allow_gather = !(eg && eg[0] == '0');
-    if (allow_gather && a->Nk <= 32 && a->ldq % 4 == 0) {     // (the decode steps of a caption search: max_length <= 32)
+    if (a->Nk <= 32 && a->ldq % 4 == 0) {     // (the decode steps of a caption search: max_length <= 32)
       if (bf) hipLaunchKernelGGL((attn_f32_arena_gather_kernel<bf16, 4>), dim3((units + 3) / 4), dim3(256), 0, s, p);
       else hipLaunchKernelGGL((attn_f32_arena_gather_kernel<f16, 4>), dim3((units + 3) / 4), dim3(256), 0, s, p);
     } else if (bf) hipLaunchKernelGGL(attn_f32_arena_kernel<bf16>, dim3((units + 3) / 4), dim3(256), 0, s, p);
@@ -2181,7 +1951,6 @@ extern "C" int vidil_attention_f32(const vidil_attn_f32_args* a, void* stream) {
                   a->kv_rows, a->Nk);
     VIDIL_REQUIRE(a->q_off == 0 && !a->causal && a->kv_len == nullptr, "attention_f32 (kv16): no q_off / causal / kv_len in this form");
     VIDIL_REQUIRE(a->out_mode >= 2 ? a->ldo % 24 == 0 : false, "attention_f32 (kv16): out_mode 2 / 3 ([hi | lo | hi] rows, planes a multiple of 8) only");
-    const int nkt = (a->Nk + 31) / 32;
     VIDIL_DISPATCH_DTYPE(a->dtype16, "attention_f32 (kv16)", {
       AttnP<T> q{};
       q.k = (const T*)(const void*)a->k; q.vt = (const T*)(const void*)a->v; q.out = (T*)a->out;
@@ -2189,28 +1958,7 @@ extern "C" int vidil_attention_f32(const vidil_attn_f32_args* a, void* stream) {
       q.Bq = a->Bq; q.H = a->H; q.Nq = a->Nq; q.Nk = a->Nk; q.Tq_cap = a->Nq; q.Tk_cap = a->kv_rows; q.NP = a->kv_rows;
       q.kv_group = a->kv_group; q.ldo = (int)a->ldo; q.n_kv = units; q.out_mode = a->out_mode; q.tiled = 1; q.rb = 1;
       q.q32 = a->q; q.ldq32 = a->ldq; q.q_scale = a->scale;
-      const dim3 g(1, a->H, units);
-      if (direct1_enabled(q)) return launch_direct1<T, true>(q, s);
-      switch (nkt) {
-        case 1: hipLaunchKernelGGL((attn_direct_kernel<T, 1, true>), g, dim3(256), 0, s, q); break;
-        case 2: hipLaunchKernelGGL((attn_direct_kernel<T, 2, true>), g, dim3(256), 0, s, q); break;
-        case 3: hipLaunchKernelGGL((attn_direct_kernel<T, 3, true>), g, dim3(256), 0, s, q); break;
-        case 4: hipLaunchKernelGGL((attn_direct_kernel<T, 4, true>), g, dim3(256), 0, s, q); break;
-        case 5: hipLaunchKernelGGL((attn_direct_kernel<T, 5, true>), g, dim3(256), 0, s, q); break;
-        case 6: hipLaunchKernelGGL((attn_direct_kernel<T, 6, true>), g, dim3(256), 0, s, q); break;
-        case 7: {
-          const char* ev = vidil_dev_env("VIDIL_ATTN_QS_VARIANT");
-          const int var = ev ? atoi(ev) : 2;      // (one key tile per wave and round, three waves per SIMD: 638 -> 555 us per 3,584-image launch)
-          // (variant 1 — two key tiles per wave at three waves per SIMD — spills 27 registers: 602 us; not built any more)
-          if (var == 2) hipLaunchKernelGGL((attn_direct_kernel<T, 7, true, 2>), g, dim3(256), 0, s, q);
-          else hipLaunchKernelGGL((attn_direct_kernel<T, 7, true>), g, dim3(256), 0, s, q);
-          break;
-        }
-        case 8: hipLaunchKernelGGL((attn_direct_kernel<T, 8, true>), g, dim3(256), 0, s, q); break;
-        default: hipLaunchKernelGGL((attn_direct_kernel<T, 24, true>), g, dim3(256), 0, s, q); break;
-      }
-      VIDIL_CHECK_LAUNCH("attention_f32 (kv16 direct)");
-      return VIDIL_OK;
+      return launch_direct1<T, true>(q, s);
     });
   }
   VIDIL_REQUIRE(a->kv16 == 0, "attention_f32: kv16 needs arith == 1");
@@ -2219,28 +1967,19 @@ extern "C" int vidil_attention_f32(const vidil_attn_f32_args* a, void* stream) {
     // waves without rows: they still stage)
     VIDIL_REQUIRE((a->out_mode >= 2 ? a->ldo % 12 == 0 : a->ldo % 4 == 0) && ((uintptr_t)a->out & 15) == 0,
                   "attention_f32 (split): output rows must allow 8-byte (split3) / 16-byte (f32) stores");
-    // 4 waves (128 rows) per workgroup. The 8-wave form (one staging of a unit's K / V serves up to 256 rows: $VIDIL_ATTN_SPLIT_NW=8)
-    // measured 2 - 12 % slower on a tower's 197 rows at 512 ... 3584 images and 0.8 % slower end to end (round 5):
-    // 59 of its 256 rows are padding, and the staging it saves was not what bounds the kernel
-    const char* ew = vidil_dev_env("VIDIL_ATTN_SPLIT_NW");
-    const int nw = ew ? atoi(ew) : 4;
-    if (nw == 8) {
-      const dim3 gridm((max_rows + 255) / 256, a->H, units);
-      if (bf) hipLaunchKernelGGL((attn_split_kernel<bf16, 8>), gridm, dim3(512), 0, s, p);
-      else hipLaunchKernelGGL((attn_split_kernel<f16, 8>), gridm, dim3(512), 0, s, p);
-    } else {
-      const dim3 gridm((max_rows + 127) / 128, a->H, units);
-      if (bf) hipLaunchKernelGGL((attn_split_kernel<bf16, 4>), gridm, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((attn_split_kernel<f16, 4>), gridm, dim3(256), 0, s, p);
-    }
+    // 4 waves (128 rows) per workgroup. An 8-wave form (one staging of a unit's K / V serves up to 256 rows) measured 2 - 12 %
+    // slower on a tower's 197 rows at 512 ... 3584 images and 0.8 % slower end to end (round 5): 59 of its 256
+    // rows are padding, and the staging it saves was not what bounds the kernel
+    const dim3 gridm((max_rows + 127) / 128, a->H, units);
+    if (bf) hipLaunchKernelGGL((attn_split_kernel<bf16, 4>), gridm, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((attn_split_kernel<f16, 4>), gridm, dim3(256), 0, s, p);
     VIDIL_CHECK_LAUNCH("attention_f32 (split)");
     return VIDIL_OK;
   }
   VIDIL_REQUIRE(a->arith == 0, "attention_f32: arith=%d (0: f32, 1: split-operand)", a->arith);
   // units of more than 8 query rows (the towers, the ITM encoder, prompt passes): the f32-MFMA kernel, 128 rows per workgroup;
   // a few rows per unit (the decode steps' cross-attention: 3 beams per image): the VALU kernel, which skips idle row groups
-  static const bool allow_mfma = [] { const char* e = getenv("VIDIL_ATTN_F32_MFMA"); return !(e && e[0] == '0'); }();
-  if (allow_mfma && max_rows > 8 && (a->out_mode >= 2 ? a->ldo % 12 == 0 : a->ldo % 4 == 0) && ((uintptr_t)a->out & 15) == 0) {   // (16-B / 8-B row stores)
+  if (max_rows > 8 && (a->out_mode >= 2 ? a->ldo % 12 == 0 : a->ldo % 4 == 0) && ((uintptr_t)a->out & 15) == 0) {   // (16-B / 8-B row stores)
     const dim3 gridm((max_rows + 127) / 128, a->H, units);
     if (bf) hipLaunchKernelGGL(attn_f32_mfma_kernel<bf16>, gridm, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(attn_f32_mfma_kernel<f16>, gridm, dim3(256), 0, s, p);

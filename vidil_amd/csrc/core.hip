@@ -13,7 +13,7 @@ void vidil_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-// Developer overrides ($VIDIL_GEMM4W, $VIDIL_GEMM4W128, $VIDIL_GEMM_CUS ...) are consulted on every GEMM launch, including
+// Developer overrides ($VIDIL_GEMM4W, $VIDIL_GEMM4W128, $VIDIL_ATTN_STREAM) are consulted on every launch, including
 // launches being captured into the decode steps' graphs: each is looked up in the environment ONCE per process and
 // remembered — unless $VIDIL_DEV_ENV is set when the first one is asked for: the tests and tools that flip these
 // switches between launches set it, and then every query is a live getenv.
@@ -72,6 +72,6 @@ const char* vidil_dev_env(const char* name) {
 }
 
 extern "C" const char* vidil_last_error(void) { return g_err; }
-extern "C" int vidil_abi_version(void) { return 12; }
+extern "C" int vidil_abi_version(void) { return 13; }
 // keep in sync with include/vidil_hip.h (tests/test_abi.py parses the header)
-extern "C" int vidil_num_entry_points(void) { return 29; }
+extern "C" int vidil_num_entry_points(void) { return 28; }

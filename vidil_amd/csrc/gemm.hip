@@ -495,14 +495,8 @@ int dispatch(const vidil_gemm_args& a, hipStream_t s) {
 // split_k (the parity precision mode's operands, see include/vidil_hip.h): which launches run the in-loop compensated product
 // (gemm4w's C3 form) — a property of the CALL (epilogue, alignment), never of its size, so that a row's result does not depend
 // on the batch around it; everything else runs the same operands as a plain GEMM with K = 3 Kl (the K-tripled form of rounds 3-4).
-static bool c3_switched_off() {
-  static const bool off = [] { const char* e = getenv("VIDIL_GEMM_C3"); return e && e[0] == '0'; }();    // (A/B switch)
-  return off;
-}
-extern "C" int vidil_gemm_split_k_in_loop(void) { return c3_switched_off() ? 0 : 1; }
-
 bool vidil_gemm_c3_serves(const vidil_gemm_args& a) {
-  if (!a.split_k || c3_switched_off()) return false;
+  if (!a.split_k) return false;
   if (a.dtype == VIDIL_DT_FP8 || a.ln_fold || a.ln_stats_out || a.rln_gamma || a.K % 96 != 0) return false;
   if (!(a.epi == VIDIL_EPI_F32 || a.epi == VIDIL_EPI_PATCH || (a.epi == VIDIL_EPI_HEADS && a.T >= 8))) return false;
   return vidil_gemm256_eligible(a, true);
@@ -527,8 +521,8 @@ extern "C" int vidil_gemm(const vidil_gemm_args* args, void* stream) {
   }
   if (args->split_k == 2) {
     // the caller wrote planes hi | lo of the A rows only: the plain K = 3 Kl product below would read plane 2
-    vidil_set_error("gemm/split_k=2: this call does not qualify for the K-loop compensated product (epi=%d T=%d K=%d, alignment, or "
-                    "$VIDIL_GEMM_C3=0) and its A rows hold planes hi | lo only — produce three planes and pass split_k=1", args->epi,
+    vidil_set_error("gemm/split_k=2: this call does not qualify for the K-loop compensated product (epi=%d T=%d K=%d or alignment) "
+                    "and its A rows hold planes hi | lo only — produce three planes and pass split_k=1", args->epi,
                     args->T, args->K);
     return VIDIL_EINVAL;
   }

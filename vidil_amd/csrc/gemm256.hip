@@ -363,13 +363,8 @@ int launch256(const vidil_gemm_args& a, hipStream_t s) {
   if (const int rc_ = vidil_lds_opt_in(attr_set, (const void*)kern, lds, "gemm256")) return rc_;
   const int num_cu = vidil_cu_count() & ~7;     // (per device: core.hip)
   // persistent grid: one workgroup per CU (a multiple of 8 so every XCD gets the same number), never more than tiles
-  int cus = num_cu;
-  if (const char* e = vidil_dev_env("VIDIL_GEMM_CUS")) {      // developer: a stream confined to fewer CUs by a CU mask (tools/exp_cu_mask.py)
-    const int v = atoi(e) & ~7;
-    if (v >= 8 && v < cus) cus = v;
-  }
   const int ntiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
-  const int tiles = !(kPersistent<EPI> && sizeof(T) == 2 && !RLN) ? ntiles : ntiles >= cus ? cus : (ntiles >= 8 ? ((ntiles + 7) & ~7) : ntiles);   // (rounded UP: gemm4w.hip launch4w)
+  const int tiles = !(kPersistent<EPI> && sizeof(T) == 2 && !RLN) ? ntiles : ntiles >= num_cu ? num_cu : (ntiles >= 8 ? ((ntiles + 7) & ~7) : ntiles);   // (rounded UP: gemm4w.hip launch4w)
   hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), lds, s, a);
   VIDIL_CHECK_LAUNCH("gemm256");
   return VIDIL_OK;
@@ -472,19 +467,15 @@ int vidil_gemm4w_launch(const vidil_gemm_args& a, hipStream_t s, int tm);   // g
 // row-partials producers (-4..5 %, with or without the residual LayerNorm) and the per-head scatter (-2..3 %) once there
 // are a couple of tiles per CU, and loses on the plain f32 epilogue (+7 %) and on small grids (and is not built for fp8
 // operands).  $VIDIL_GEMM4W = 0 / 1 forces one kernel (developer).
-#ifndef VIDIL_GEMM4W_F32_DEFAULT
-#define VIDIL_GEMM4W_F32_DEFAULT -1   // (-1: by K, see prefer_4w)
-#endif
 static bool prefer_4w(const vidil_gemm_args& a) {
   if (a.epi == VIDIL_EPI_HEADS && a.T < 8) return false;   // (the 4-wave scatter steps (image, token) by 8 rows: gemm_epilogue.inc)
   if (const char* e = vidil_dev_env("VIDIL_GEMM4W")) return atoi(e) != 0;
   const long tiles = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
   // (1.5 workgroup rounds: 384 tiles on 256 CUs)
-  static const long min_tiles = [] { const char* e = getenv("VIDIL_GEMM4W_MIN_TILES"); return e ? atol(e) : 3L * vidil_cu_count() / 2; }();
-  if (a.dtype == VIDIL_DT_FP8) {   // (round 4: the 4-wave main loop takes e4m3 operands too; same grid rule, plain epilogues;
-    //                                $VIDIL_GEMM4W_FP8=0 keeps the fp8 GEMMs on the 8-wave kernel: the A/B of DESIGN.md §5)
-    static const bool fp8_4w = [] { const char* e = getenv("VIDIL_GEMM4W_FP8"); return !(e && e[0] == '0'); }();
-    return fp8_4w && tiles >= min_tiles &&
+  static const long min_tiles = 3L * vidil_cu_count() / 2;
+  if (a.dtype == VIDIL_DT_FP8) {   // (round 4: the 4-wave main loop takes e4m3 operands too; same grid rule, plain epilogues:
+    //                                the A/B against the 8-wave kernel is DESIGN.md §5)
+    return tiles >= min_tiles &&
            (a.epi == VIDIL_EPI_F8 || a.epi == VIDIL_EPI_HEADS || (a.epi == VIDIL_EPI_F32 && a.act == VIDIL_ACT_NONE));
   }   // (developer sweep, whole bench, same box: 512 -> 5,112, 384 -> 5,120, 320 -> 5,094, 128 -> 5,050 frames/s — small grids start faster on gemm256)
   if (tiles < min_tiles) return false;
@@ -498,10 +489,9 @@ static bool prefer_4w(const vidil_gemm_args& a) {
       // the LN-fold producers, with or without a residual LayerNorm: always; the plain f32 epilogue (the parity mode's K-tripled
       // GEMMs, the towers' last fc2, the LM head) by K: with 4 output bytes per 2K flop the f32 stores weigh on short reductions —
       // round 4, same box, whole bench: the last-block fc2 (K = 3072) 1,040 -> 1,160 TFLOP/s on the 4-wave kernel, the LM head
-      // (10,752 x 30,524, K = 768) 838 -> 708.  $VIDIL_GEMM4W_F32 = 0 / 1 forces one kernel (A/B switch).
-      static const int f32_4w = [] { const char* e = getenv("VIDIL_GEMM4W_F32"); return e ? atoi(e) : VIDIL_GEMM4W_F32_DEFAULT; }();
+      // (10,752 x 30,524, K = 768) 838 -> 708.
       // (round 5: with or without an activation — the parity mode's K-tripled fc1 + GELU, K = 2304, ran on the 8-wave kernel)
-      return a.ln_stats_out != nullptr || f32_4w > 0 || (f32_4w < 0 && a.K >= 1536);
+      return a.ln_stats_out != nullptr || a.K >= 1536;
     }
     default:
       return false;

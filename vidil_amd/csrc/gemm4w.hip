@@ -112,23 +112,8 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
   const int lda = p.lda > 0 ? p.lda : K;
   const int tiles_n = (N + 255) >> 8;
   const int tiles_m = (M + (1 << MSH) - 1) >> MSH;
-  // developer experiment: a COLUMN-BLOCKED tile walk — blocks of `cblk` column tiles, all row panels
-  // inside a block — so that the W rows an XCD works on at any one time stay inside its 4-MiB L2 (launch4w copies
-  // $VIDIL_4W_COLBLOCK into the patch epilogue's `tpi` field for the other epilogues; 0 = the row-major walk)
-  // (compiled in only with -DVIDIL_4W_COLBLOCK_EXP: the extra uniform state costs the hot instantiations 7-10 more spilled
-  //  registers, which is not a price the shipped kernels pay for a developer knob)
-#ifdef VIDIL_4W_COLBLOCK_EXP
-  const int cblk = EPI == VIDIL_EPI_PATCH ? 0 : p.tpi;
-#endif
+  // row-major tile walk (a column-blocked walk, to keep an XCD's W rows inside its L2, measured no gain: DESIGN.md §7 (t))
   auto tile_of = [&](int lt, int& tm, int& tn) {
-#ifdef VIDIL_4W_COLBLOCK_EXP
-    if (cblk > 0) {
-      const int per = tiles_m * cblk, cbk = lt / per, r = lt - cbk * per;
-      tm = r / cblk;
-      tn = cbk * cblk + (r - tm * cblk);
-      return;
-    }
-#endif
     tm = lt / tiles_n;
     tn = lt - tm * tiles_n;
   };
@@ -565,46 +550,17 @@ int launch4w(const vidil_gemm_args& a, hipStream_t s) {
   constexpr int LDS_BYTES = kLds<TM>;
   if (const int rc_ = vidil_lds_opt_in(attr_set, (const void*)kern, LDS_BYTES, "gemm4w")) return rc_;
   const int num_cu = vidil_cu_count() & ~7;     // (per device: core.hip)
-  int cus = num_cu;
-  if (const char* e = vidil_dev_env("VIDIL_GEMM_CUS")) {
-    const int v = atoi(e) & ~7;
-    if (v >= 8 && v < cus) cus = v;
-  }
   const int ntiles = ((a.M + 64 * TM - 1) / (64 * TM)) * ((a.N + 255) / 256);
   // (fewer tiles than CUs: one workgroup per tile — the count rounded UP to the XCD multiple, the spare workgroups find
   //  their XCD's range empty and leave; rounded down, a few workgroups would run two tiles and double the launch's time)
-  const int tiles = ntiles >= cus ? cus : (ntiles >= 8 ? ((ntiles + 7) & ~7) : ntiles);
-#ifdef VIDIL_4W_COLBLOCK_EXP
-  vidil_gemm_args a2 = a;
-  if constexpr (EPI != VIDIL_EPI_PATCH) {
-    a2.tpi = 0;
-    if (const char* e = vidil_dev_env("VIDIL_4W_COLBLOCK")) {       // developer: column-blocked tile walk (see the kernel)
-      const int cb = atoi(e), tn = (a.N + 255) / 256;
-      if (cb > 0 && cb < tn && tn % cb == 0) a2.tpi = cb;
-    }
-  }
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), LDS_BYTES, s, a2);
-#else
+  const int tiles = ntiles >= num_cu ? num_cu : (ntiles >= 8 ? ((ntiles + 7) & ~7) : ntiles);
   hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), LDS_BYTES, s, a);
-#endif
   VIDIL_CHECK_LAUNCH("gemm4w");
   return VIDIL_OK;
 }
 
 template <typename T>
 int launch4w_dispatch(const vidil_gemm_args& a, hipStream_t s) {
-#ifdef VIDIL_4W_DEV_ONE   // developer builds (ISA inspection): one instantiation, VIDIL_4W_DEV_ONE = 1 fc1 (LN fold + GELU), 2 f32 + residual + row partials, 3 LN-folded heads, 4 = 2 + residual LayerNorm, 5 plain heads, 6 plain 16-bit
-  if constexpr (VIDIL_4W_DEV_ONE == 1) return launch4w<T, VIDIL_EPI_F16, VIDIL_ACT_GELU_ERF, true>(a, s);
-  if constexpr (VIDIL_4W_DEV_ONE == 2) return launch4w<T, VIDIL_EPI_F32, VIDIL_ACT_NONE, false, T, true>(a, s);
-  if constexpr (VIDIL_4W_DEV_ONE == 3) return launch4w<T, VIDIL_EPI_HEADS, VIDIL_ACT_NONE, true>(a, s);
-  if constexpr (VIDIL_4W_DEV_ONE == 4) return launch4w<T, VIDIL_EPI_F32, VIDIL_ACT_NONE, false, T, true, true>(a, s);
-  if constexpr (VIDIL_4W_DEV_ONE == 5) return launch4w<T, VIDIL_EPI_HEADS, VIDIL_ACT_NONE>(a, s);
-  if constexpr (VIDIL_4W_DEV_ONE == 6) return launch4w<T, VIDIL_EPI_F16, VIDIL_ACT_NONE>(a, s);
-  if constexpr (VIDIL_4W_DEV_ONE == 7) return launch4w<fp8, VIDIL_EPI_F8, VIDIL_ACT_GELU_ERF, false, T>(a, s);     // (fp8 operands)
-  if constexpr (VIDIL_4W_DEV_ONE == 8) return launch4w<fp8, VIDIL_EPI_HEADS, VIDIL_ACT_NONE, false, T>(a, s);
-  if constexpr (VIDIL_4W_DEV_ONE == 9) return launch4w<fp8, VIDIL_EPI_F32, VIDIL_ACT_NONE, false, T>(a, s);
-  return -1000;
-#else
   if (a.ln_fold) {
     if (a.epi == VIDIL_EPI_HEADS) return launch4w<T, VIDIL_EPI_HEADS, VIDIL_ACT_NONE, true>(a, s);
     if (a.epi == VIDIL_EPI_ARENA) return launch4w<T, VIDIL_EPI_ARENA, VIDIL_ACT_NONE, true>(a, s);     // (round 6: the decode steps' Q|K|V)
@@ -630,7 +586,6 @@ int launch4w_dispatch(const vidil_gemm_args& a, hipStream_t s) {
     default:
       return launch4w<T, VIDIL_EPI_PATCH, VIDIL_ACT_NONE>(a, s);
   }
-#endif
 }
 
 }  // namespace
@@ -638,9 +593,6 @@ int launch4w_dispatch(const vidil_gemm_args& a, hipStream_t s) {
 // the 128 x 256-tile form: plain epilogues only (the decode steps' projections and FFN, mid-size grids)
 template <typename T>
 int launch4w128_dispatch(const vidil_gemm_args& a, hipStream_t s) {
-#ifdef VIDIL_4W_DEV_ONE
-  return -1000;
-#else
   if (a.ln_fold || a.ln_stats_out || a.rln_gamma) return -1000;
   switch (a.epi) {
     case VIDIL_EPI_F16:
@@ -657,16 +609,12 @@ int launch4w128_dispatch(const vidil_gemm_args& a, hipStream_t s) {
     default:
       return -1000;
   }
-#endif
 }
 
 // fp8 operands (round 4): the tower mode's GEMMs — fp8 hand-over with / without activation, per-head scatter into the 16-bit
 // companion type, f32 + residual — on the 4-wave main loop (K-tiles of 128 e4m3, v_mfma_scale_f32_32x32x64_f8f6f4)
 template <typename TO>
 static int launch4w_fp8(const vidil_gemm_args& a, hipStream_t s) {
-#ifdef VIDIL_4W_DEV_ONE
-  return -1000;
-#else
   if (a.ln_fold || a.ln_stats_out || a.rln_gamma || a.out16) return -1000;
   switch (a.epi) {
     case VIDIL_EPI_F32:
@@ -680,7 +628,6 @@ static int launch4w_fp8(const vidil_gemm_args& a, hipStream_t s) {
     default:
       return -1000;
   }
-#endif
 }
 
 // split_k launches (the parity precision mode's GEMMs): the in-loop compensated product, at EVERY size — 256-row tiles once they
@@ -704,14 +651,10 @@ static int launch4w_c3_tm(const vidil_gemm_args& a, hipStream_t s) {
   }
 }
 int vidil_gemm4w_c3_launch(const vidil_gemm_args& a, hipStream_t s) {
-#ifdef VIDIL_4W_DEV_ONE
-  return -1000;
-#else
   const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
   const bool big = t256 >= 5L * vidil_cu_count() / 8 || a.epi == VIDIL_EPI_PATCH;      // (the patch epilogue is built for 256-row tiles only)
   if (a.dtype == VIDIL_DT_BF16) return big ? launch4w_c3_tm<bf16, 4>(a, s) : launch4w_c3_tm<bf16, 2>(a, s);
   return big ? launch4w_c3_tm<f16, 4>(a, s) : launch4w_c3_tm<f16, 2>(a, s);
-#endif
 }
 
 // tm: 4 = 256 x 256 tiles, 2 = 128 x 256 tiles.  -1000: the variant is not built here.
@@ -719,8 +662,5 @@ int vidil_gemm4w_launch(const vidil_gemm_args& a, hipStream_t s, int tm) {
   if (a.dtype == VIDIL_DT_FP8) return tm == 4 ? (a.dtype16 == VIDIL_DT_BF16 ? launch4w_fp8<bf16>(a, s) : launch4w_fp8<f16>(a, s)) : -1000;
   if (tm == 2) return a.dtype == VIDIL_DT_BF16 ? launch4w128_dispatch<bf16>(a, s) : launch4w128_dispatch<f16>(a, s);
   if (a.dtype == VIDIL_DT_BF16) return launch4w_dispatch<bf16>(a, s);
-#ifdef VIDIL_4W_DEV_ONE
-  return -1000;
-#endif
   return launch4w_dispatch<f16>(a, s);
 }

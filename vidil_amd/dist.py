@@ -102,9 +102,7 @@ _GATHER_BACKENDS = ("nccl", "gloo")
 
 
 def _gather_supported():
-    """Same answer on every rank by construction: the environment switch and the backend's name, nothing measured."""
-    if os.environ.get("VIDIL_GATHER", "gather") == "allgather":
-        return False
+    """Same answer on every rank by construction: the backend's name, nothing measured."""
     return str(dist.get_backend()).lower() in _GATHER_BACKENDS
 
 
@@ -144,7 +142,7 @@ def gather_json(obj):
     rank 0 merges and writes).  RCCL (backend 'nccl') moves device buffers over xGMI, Gloo moves host buffers.  The same code
     path runs for every world size including 1, so what an 8-GPU job executes is what the one-GPU box has already executed
     (tests/test_dist_gpu.py).  A true gather since round 5; ``all_gather`` of the payloads remains for a backend known not to
-    implement ``gather`` and behind $VIDIL_GATHER=allgather (``_gather_supported``: decided before the collective)."""
+    implement ``gather`` (``_gather_supported``: decided before the collective)."""
     if not is_dist_avail_and_initialized():
         return [obj]
     dev = _comm_device()

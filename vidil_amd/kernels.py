@@ -7,6 +7,7 @@ All functions raise ``VidilHipError`` on a non-zero return code.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
@@ -99,18 +100,11 @@ def gemm(a, w, bias=None, **kw):
     return ret
 
 
-def split_k_in_loop() -> bool:
-    """True when the library forms the parity mode's compensated products inside one K loop (vidil_gemm_split_k_in_loop): such a
-    consumer reads planes hi | lo of its [hi | lo | hi] operand rows only, so a producer may leave the third plane unwritten
-    (``gemm(..., split3_out=, split3_planes=2)``)."""
-    return bool(_lib.load().vidil_gemm_split_k_in_loop())
-
-
 def split_k_serves(a, w, bias=None, **kw) -> bool:
     """Per CALL (vidil_gemm_split_k_serves): True when ``gemm(a, w, bias, split_k=True, **kw)`` would take the K-loop form and
     read planes hi | lo of ``a`` only.  A producer may leave the third plane of its rows unwritten only if this holds for EVERY
-    consumer of those rows (process-wide ``split_k_in_loop()`` is necessary, not sufficient: the per-head epilogue with fewer
-    than 8 tokens per sequence, or an unaligned vector, takes the plain K = 3 Kl product).  Launches nothing."""
+    consumer of those rows (the per-head epilogue with fewer than 8 tokens per sequence, or an unaligned vector, takes the plain
+    K = 3 Kl product).  Launches nothing."""
     kw = dict(kw, split_k=True)
     kw.pop("a_planes", None)
     g, _ = _gemm_build(a, w, bias, **kw)
@@ -118,6 +112,14 @@ def split_k_serves(a, w, bias=None, **kw) -> bool:
     if rc < 0:
         check(rc, "gemm_split_k_serves")
     return rc == 1
+
+
+def poison_third_plane(planes, *bufs):
+    """Developer check ($VIDIL_POISON_SPLIT3=1): with planes == 2, fill the unwritten third plane of each [hi | lo | hi] operand
+    buffer with NaNs, so that any consumer that reads one shows up at once."""
+    if planes == 2 and os.environ.get("VIDIL_POISON_SPLIT3") == "1":
+        for b in bufs:
+            b[:, 2 * (b.shape[1] // 3):] = float("nan")
 
 
 def gemm_kernel_name(a, w, bias=None, **kw):
@@ -252,7 +254,7 @@ def _gemm_build(a, w, bias=None, *, out=None, out_dtype=None, act=ACT_NONE, resi
 def layernorm(x, gamma, beta, eps, *, M=None, D=None, x_stride=None, out16=None, out32=None, split3=False, planes=3):
     """LayerNorm rows of f32 ``x``.  Rows are ``x_stride`` elements apart (default dense).
     split3: ``out16`` is [M, 3D] and receives the error-compensated operand rows [hi | lo | hi] (VIDIL_DT_SPLIT3); planes=2
-    (VIDIL_DT_SPLIT2): only hi | lo are written — for consumers that are split_k GEMMs in the K-loop form (split_k_in_loop())."""
+    (VIDIL_DT_SPLIT2): only hi | lo are written — for consumers that are split_k GEMMs in the K-loop form (split_k_serves())."""
     lib = _lib.load()
     D = D if D is not None else x.shape[-1]
     M = M if M is not None else x.numel() // D

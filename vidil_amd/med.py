@@ -362,10 +362,9 @@ class BertModel(PackedCache, nn.Module):
         if fused is None:
             # encoder batches with cross-attention (the ITM pairs) run without LayerNorm launches, WHATEVER their size: a
             # pair's logits must not depend on how many other pairs share its batch (ranks / tail batches of different
-            # sizes write the same JSON), so the choice cannot depend on M ($VIDIL_FUSE_LN_MIN_ROWS is for experiments).
+            # sizes write the same JSON), so the choice cannot depend on M.
             # Decoder sessions (arena) state their choice themselves (DecoderSession.fused_ln), for the same reason.
-            fused = (self._text_fold_ok(cdt) and cross is not None and arena is None and not stop_after_self
-                     and M >= int(os.environ.get("VIDIL_FUSE_LN_MIN_ROWS", 0)))
+            fused = self._text_fold_ok(cdt) and cross is not None and arena is None and not stop_after_self
         elif fused and not (self._text_fold_ok(cdt) and cross is not None and not stop_after_self):
             raise K.VidilHipError("run_layers(fused=True): the LN-folded text stack needs cross-attention layers, 16-bit operands and "
                                   "hidden_size % 64 == 0, <= 1024")
@@ -458,31 +457,26 @@ class BertModel(PackedCache, nn.Module):
         tmp = torch.empty((M, C), dtype=torch.float32, device=dev)
         inter3 = torch.empty((M, 3 * cfg.intermediate_size), dtype=cdt, device=dev)
         # Which producers may leave the third plane of their [hi | lo | hi] rows unwritten: only those whose EVERY
-        # consumer takes the K-loop form of the compensated product, asked per CALL (K.split_k_serves: the process-wide switch
-        # is necessary, not sufficient).  inter3 feeds fc2 (f32 epilogue); with the f32-row attention kinds h3 / o3 feed Q|K|V,
-        # the cross query, both output projections and fc1, all with the f32 epilogue; kind "16" feeds h3 to arena / short-sequence
-        # scatter epilogues, which run the plain K = 3 Kl product over all three planes.  The consumers state a_planes, so a
-        # launch that would read an unwritten plane fails (EINVAL) instead of computing on it.
+        # consumer takes the K-loop form of the compensated product, asked per CALL (K.split_k_serves).  inter3 feeds fc2 (f32
+        # epilogue); with the f32-row attention kinds h3 / o3 feed Q|K|V, the cross query, both output projections and fc1, all
+        # with the f32 epilogue; kind "16" feeds h3 to arena / short-sequence scatter epilogues, which run the plain K = 3 Kl
+        # product over all three planes.  The consumers state a_planes, so a launch that would read an unwritten plane fails
+        # (EINVAL) instead of computing on it.
         f32_attn, arith = parity_attention_f32(self), parity_attention_arith(self)
         qkv32 = torch.empty((M, 3 * C), dtype=torch.float32, device=dev) if f32_attn else None
         q32 = torch.empty((M, C), dtype=torch.float32, device=dev) if f32_attn and cross is not None else None
         d0 = p["layers"][0]
         planes = planes_h = 3
-        if K.split_k_in_loop():
-            if K.split_k_serves(inter3, d0["o_w3"], d0["o_b"], out=tmp, resid=h32):
-                planes = 2
-            if f32_attn and planes == 2 and all((
-                    K.split_k_serves(h3, d0["qkv_w3"], d0["qkv_b"], out=qkv32),
-                    K.split_k_serves(o3, d0["ao_w3"], d0["ao_b"], out=tmp, resid=h32),
-                    K.split_k_serves(h3, d0["i_w3"], d0["i_b"], split3_out=inter3, act=K.ACT_GELU_ERF),
-                    cross is None or K.split_k_serves(h3, d0["cq_w3"], d0["cq_b"], out=q32))):
-                planes_h = 2
-        if planes == 2 and os.environ.get("VIDIL_POISON_SPLIT3") == "1":       # (developer: NaNs in the unwritten third planes —
-            for _b in (inter3,):                               #  any consumer that reads one shows up at once)
-                _b[:, 2 * (_b.shape[1] // 3):] = float("nan")
-        if planes_h == 2 and os.environ.get("VIDIL_POISON_SPLIT3") == "1":       # (developer: NaNs in the unwritten third planes —
-            for _b in (o3, h3,):                               #  any consumer that reads one shows up at once)
-                _b[:, 2 * (_b.shape[1] // 3):] = float("nan")
+        if K.split_k_serves(inter3, d0["o_w3"], d0["o_b"], out=tmp, resid=h32):
+            planes = 2
+        if f32_attn and planes == 2 and all((
+                K.split_k_serves(h3, d0["qkv_w3"], d0["qkv_b"], out=qkv32),
+                K.split_k_serves(o3, d0["ao_w3"], d0["ao_b"], out=tmp, resid=h32),
+                K.split_k_serves(h3, d0["i_w3"], d0["i_b"], split3_out=inter3, act=K.ACT_GELU_ERF),
+                cross is None or K.split_k_serves(h3, d0["cq_w3"], d0["cq_b"], out=q32))):
+            planes_h = 2
+        K.poison_third_plane(planes, inter3)
+        K.poison_third_plane(planes_h, o3, h3)
         Nk = t_off + T
         if arena is not None and T > 1 and t_off != 0:
             raise K.VidilHipError("run_layers: a multi-token block can only be appended to a beam arena at position 0")

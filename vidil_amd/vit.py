@@ -242,23 +242,20 @@ class VisionTransformer(PackedCache, nn.Module):
         o3 = torch.empty((M, 3 * D), dtype=cdt, device=dev)
         hid3 = torch.empty((M, 3 * Dh), dtype=cdt, device=dev)
         # (a consumer that takes the K-loop form of the compensated product reads planes hi | lo of its operand rows only, so their
-        #  producer need not write the third — decided per CALL from the blocks' actual consumers (the process-wide
-        #  switch alone is not enough, e.g. the per-head epilogue with fewer than 8 tokens runs the plain K = 3 Kl product); the
+        #  producer need not write the third — decided per CALL from the blocks' actual consumers (e.g. the per-head
+        #  epilogue with fewer than 8 tokens runs the plain K = 3 Kl product); the
         #  consumers then state a_planes, so a launch that would read an unwritten plane fails instead of computing on it)
         f32_attn, arith = parity_attention_f32(self), parity_attention_arith(self)
         qkv32 = torch.empty((M, 3 * D), dtype=torch.float32, device=dev) if f32_attn else None
         b3 = next((b for b in p["blocks"] if "qkv_w3" in b), None)
         planes = 3
-        if b3 is not None and K.split_k_in_loop():
+        if b3 is not None:
             qkv_kw = dict(out=qkv32) if f32_attn else dict(heads=heads)
             if (K.split_k_serves(a3, b3["qkv_w3"], b3["qkv_b"], **qkv_kw) and K.split_k_serves(o3, b3["proj_w3"], b3["proj_b"], out=x, resid=x)
                     and K.split_k_serves(a3, b3["fc1_w3"], b3["fc1_b"], split3_out=hid3, act=K.ACT_GELU_ERF)
                     and K.split_k_serves(hid3, b3["fc2_w3"], b3["fc2_b"], out=x, resid=x)):
                 planes = 2
-        import os
-        if planes == 2 and os.environ.get("VIDIL_POISON_SPLIT3") == "1":       # (developer: NaNs in the unwritten third planes —
-            for _b in (a3, o3, hid3,):                               #  any consumer that reads one shows up at once)
-                _b[:, 2 * (_b.shape[1] // 3):] = float("nan")
+        K.poison_third_plane(planes, a3, o3, hid3)
         plain = [b for b in p["blocks"] if "qkv_w3" not in b]
         if plain:       # mixed form: the leading blocks on plain 16-bit operands (unfused: LayerNorm kernel + plain GEMM)
             xn = torch.empty((M, D), dtype=cdt, device=dev)
