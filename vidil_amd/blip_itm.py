@@ -40,7 +40,8 @@ class BLIP_ITM(PackedCache, nn.Module):
         p = dict(itm_w=w16(self.itm_head.weight, dtype=self.cdt), itm_b=v32(self.itm_head.bias), parity=self.parity)
         if p["parity"]:          # parity precision mode: [W_hi | W_hi | W_lo] against the [hi | lo | hi] rows of the [CLS] states
             p["itm_w3"] = w3(self.itm_head.weight, dtype=self.cdt)
-        # the 'itc' head's two projections (models/blip_itm.py:60-67; plain operands)
+            p.update(vp_w3=w3(self.vision_proj.weight, dtype=self.cdt), tp_w3=w3(self.text_proj.weight, dtype=self.cdt))
+        # the 'itc' head's two projections (models/blip_itm.py:60-67)
         p.update(vp_w=w16(self.vision_proj.weight, dtype=self.cdt), vp_b=v32(self.vision_proj.bias),
                  tp_w=w16(self.text_proj.weight, dtype=self.cdt), tp_b=v32(self.text_proj.bias))
         return p
@@ -56,19 +57,44 @@ class BLIP_ITM(PackedCache, nn.Module):
         K.gemm(h16.view(-1), w, b, out=out, M=rows, lda=T * C)
         return K.l2_normalize_rows(out)
 
-    @torch.no_grad()
-    def itc_similarity(self, y16, n_images, captions, device):
-        """models/blip_itm.py:60-67 (match_head='itc'): normalize(vision_proj(image [CLS])) @ normalize(text_proj(text [CLS]))^T
-        with the text encoder in mode='text' (no cross-attention) -> f32 [n_images, len(captions)], exact-f32 scores."""
-        if self.parity:
-            raise NotImplementedError("match_head='itc' has no parity-precision form (it is not on the CapFilt path)")
+    def _project_cls_parity(self, h32, rows, T, w3_, b):
+        """_project_cls in the parity precision mode: from the f32 final states h32 [rows*T, C] (the parity ViT's y32, the text
+        stack's h32), token 0 of each sequence as [hi | lo | hi] rows against [W_hi | W_hi | W_lo], f32 out, then normalised."""
+        C = h32.shape[-1]
+        cls32 = h32.reshape(rows, T, C)[:, 0].contiguous()
+        a3 = K.split3(cls32, torch.empty((rows, 3 * C), dtype=w3_.dtype, device=h32.device))
+        out = torch.empty((rows, w3_.shape[0]), dtype=torch.float32, device=h32.device)
+        K.gemm(a3, w3_, b, out=out, split_k=True)
+        return K.l2_normalize_rows(out)
+
+    def image_embeds(self, y32, y16, n_images):
+        """Unit-norm ITC image embeddings [n_images, embed_dim] of the ViT output (y32 f32 [n_images, T, width], y16 its
+        16-bit companion — [hi | lo | hi] rows in the parity mode, where the f32 states are projected)."""
         p = self.packed()
-        img = self._project_cls(y16, n_images, y16.shape[0] // n_images, p["vp_w"], p["vp_b"])
+        if p["parity"]:
+            return self._project_cls_parity(y32, n_images, y32.numel() // (n_images * y32.shape[-1]), p["vp_w3"], p["vp_b"])
+        return self._project_cls(y16, n_images, y16.shape[0] // n_images, p["vp_w"], p["vp_b"])
+
+    def text_embeds(self, d_ids, d_lens):
+        """Unit-norm ITC text embeddings of right-padded ids i32 [N, T] (device) through the text encoder in mode='text'."""
+        p = self.packed()
+        h32, h16 = self.text_encoder.encode(d_ids, d_lens, None)       # mode='text': no cross-attention
+        if p["parity"]:
+            return self._project_cls_parity(h32, d_ids.shape[0], d_ids.shape[1], p["tp_w3"], p["tp_b"])
+        return self._project_cls(h16, d_ids.shape[0], d_ids.shape[1], p["tp_w"], p["tp_b"])
+
+    @torch.no_grad()
+    def itc_similarity(self, y16, n_images, captions, device, y32=None):
+        """models/blip_itm.py:60-67 (match_head='itc'): normalize(vision_proj(image [CLS])) @ normalize(text_proj(text [CLS]))^T
+        with the text encoder in mode='text' (no cross-attention) -> f32 [n_images, len(captions)], exact-f32 scores.
+        y32: the ViT's f32 output — needed in the parity precision mode, whose projections take the f32 states."""
+        if self.parity and y32 is None:
+            raise ValueError("itc_similarity (parity mode): pass the ViT's f32 output as y32=")
+        img = self.image_embeds(y32, y16, n_images)
         ids, lens = self.tokenize(list(captions))
         t_eff = max(1, min(ITM_MAX_LENGTH, int(lens.max().item())))
         d_ids = ids[:, :t_eff].to(device).contiguous()
-        _, h16 = self.text_encoder.encode(d_ids, lens.to(device).contiguous(), None)
-        txt = self._project_cls(h16, d_ids.shape[0], t_eff, p["tp_w"], p["tp_b"])
+        txt = self.text_embeds(d_ids, lens.to(device).contiguous())
         return K.scan_scores(img, txt)
 
     # ------------------------------------------------------------------ tokenisation
@@ -127,14 +153,18 @@ class BLIP_ITM(PackedCache, nn.Module):
         P = ids.shape[0] if pair_text is None else pair_text.numel()
         p = self.packed()
         if p["parity"]:
-            # parity precision mode (packing.set_parity_mode): every pair through ALL layers on all of its tokens with
-            # error-compensated GEMM operands (BertModel.encode -> _run_layers_parity) — no [CLS]-only last layer, no
-            # shared text front: a statement about results, not the throughput schedule
+            # parity precision mode (packing.set_parity_mode): every pair through the stack with error-compensated GEMM operands
+            # (_run_layers_parity), no shared text front.  With the f32-row attention kinds the last layer runs on the [CLS] rows
+            # alone (BertModel.encode_cls_parity); kind "16" takes every token through every layer (BertModel.encode)
             if pair_text is not None:
                 ids, lens = ids.index_select(0, pair_text).contiguous(), lens.index_select(0, pair_text).contiguous()
-            h32, _ = te.encode(ids, lens, cross, cross_index=image_index, cross_groups=group_start, cross_max_group=max_group)
             C = te.config.hidden_size
-            cls32 = h32.view(P, ids.shape[1], C)[:, 0].contiguous()
+            if te.cls_last_parity_ok(cross):
+                cls32, _ = te.encode_cls_parity(ids, lens, cross, cross_index=image_index, cross_groups=group_start,
+                                                cross_max_group=max_group)
+            else:
+                h32, _ = te.encode(ids, lens, cross, cross_index=image_index, cross_groups=group_start, cross_max_group=max_group)
+                cls32 = h32.view(P, ids.shape[1], C)[:, 0].contiguous()
             a3 = K.split3(cls32, torch.empty((P, 3 * C), dtype=p["itm_w"].dtype, device=dev))
             out = torch.empty((P, 2), dtype=torch.float32, device=dev)
             K.gemm(a3, p["itm_w3"], p["itm_b"], out=out, split_k=True)
@@ -153,9 +183,9 @@ class BLIP_ITM(PackedCache, nn.Module):
             raise ValueError(f"unknown match_head {match_head!r}")
         require_cuda(image, "BLIP_ITM.forward")
         F = image.shape[0]
-        _, y16 = self.visual_encoder.forward_both(image)
+        y32, y16 = self.visual_encoder.forward_both(image)
         if match_head == "itc":          # [F, F] similarities (models/blip_itm.py:60-67)
-            return self.itc_similarity(y16, F, caption, image.device)
+            return self.itc_similarity(y16, F, caption, image.device, y32=y32)
         ids, lens = self.tokenize(list(caption))
         return self.itm_pairs(y16, F, ids, lens, torch.arange(F, dtype=torch.int32))
 

@@ -19,7 +19,7 @@ import torch.nn as nn
 from . import kernels as K
 from .blip import CLIP_MEAN, CLIP_STD, load_checkpoint
 from .blip_itm import ITM_MAX_LENGTH, BLIP_ITM
-from .packing import require_cuda, v32, w16
+from .packing import require_cuda
 from .tokenizer import refuse_synthetic_with_checkpoint
 
 
@@ -31,47 +31,42 @@ class BLIP_Retrieval(BLIP_ITM):
                          vit_ckpt_layer=vit_ckpt_layer, embed_dim=embed_dim, tokenizer=tokenizer)
         self.temp = nn.Parameter(0.07 * torch.ones([]))      # models/blip_retrieval.py:66 (unused at inference)
         self.queue_size, self.momentum, self.negative_all_rank = queue_size, momentum, negative_all_rank
-        # the retrieval heads have no parity form: pin this model (and its towers) to the plain mode so that the process-wide
-        # $VIDIL_PARITY default — meant for the captioner, the filter and CLIP — leaves it working
+        # pinned to the plain mode so that the process-wide $VIDIL_PARITY default — meant for the captioner, the filter and CLIP —
+        # leaves it as it is; the parity form of this backend is an explicit per-model set_parity_mode(True, model)
         from .packing import set_parity_mode
         set_parity_mode(False, self)
 
-    def _pack(self):
-        if self.__dict__.get("_parity"):     # (explicitly switched on for THIS model)
-            raise NotImplementedError("the parity precision mode is built for BLIP_Decoder, BLIP_ITM and CLIPModel, not for the retrieval heads")
-        return super()._pack()          # (BLIP_ITM packs the two ITC projections: vp_w / vp_b / tp_w / tp_b)
-
-    # ------------------------------------------------------------------ features (_project_cls: BLIP_ITM)
+    # ------------------------------------------------------------------ features (BLIP_ITM.image_embeds / text_embeds)
+    # In the parity precision mode (set_parity_mode(True, model)) the ViT and the text stack run on error-compensated operands and
+    # the two ITC projections take their f32 [CLS] states (BLIP_ITM._project_cls_parity); the image tokens handed to ``rerank``
+    # are then the ViT's [hi | lo | hi] rows.
 
     @torch.no_grad()
     def image_features_u8(self, frames_u8):
-        """uint8 [N,S,S,3] -> (image tokens f16 [N*T, width], unit-norm embeddings f32 [N, embed_dim])."""
+        """uint8 [N,S,S,3] -> (image tokens f16 [N*T, width] — [N*T, 3*width] in the parity mode —, unit-norm embeddings f32
+        [N, embed_dim])."""
         require_cuda(frames_u8, "BLIP_Retrieval.image_features_u8")
         N = frames_u8.shape[0]
-        _, y16 = self.visual_encoder.forward_u8(frames_u8, CLIP_MEAN, CLIP_STD)
-        p = self.packed()
-        return y16, self._project_cls(y16, N, y16.shape[0] // N, p["vp_w"], p["vp_b"])
+        y32, y16 = self.visual_encoder.forward_u8(frames_u8, CLIP_MEAN, CLIP_STD)
+        return y16, self.image_embeds(y32, y16, N)
 
     @torch.no_grad()
     def image_features(self, image):
         """f32 [N,3,S,S] (normalised) -> same as image_features_u8 (run_visual_tokenization.py:152-159)."""
         require_cuda(image, "BLIP_Retrieval.image_features")
         N = image.shape[0]
-        _, y16 = self.visual_encoder.forward_both(image)
-        p = self.packed()
-        return y16, self._project_cls(y16, N, y16.shape[0] // N, p["vp_w"], p["vp_b"])
+        y32, y16 = self.visual_encoder.forward_both(image)
+        return y16, self.image_embeds(y32, y16, N)
 
     @torch.no_grad()
     def text_features(self, texts, device, batch=512):
         """list[str] -> (unit-norm f32 [N,embed_dim], ids i32 [N,35] with the first id := [ENC], lens i32 [N])."""
-        p = self.packed()
         embeds, all_ids, all_lens = [], [], []
         for i in range(0, len(texts), batch):
             ids, lens = self.tokenize(texts[i:i + batch])              # padding='max_length', max_length=35
             t_eff = max(1, min(ITM_MAX_LENGTH, int(lens.max().item())))
             d_ids = ids[:, :t_eff].to(device).contiguous()
-            _, h16 = self.text_encoder.encode(d_ids, lens.to(device).contiguous(), None)     # mode='text': no cross-attn
-            embeds.append(self._project_cls(h16, d_ids.shape[0], t_eff, p["tp_w"], p["tp_b"]))
+            embeds.append(self.text_embeds(d_ids, lens.to(device).contiguous()))
             all_ids.append(ids)
             all_lens.append(lens)
         ids = torch.cat(all_ids, 0)

@@ -1795,6 +1795,64 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_split_kernel(const AttnF32P p
     }
 }
 
+// SPLIT-OPERAND form for units of ONE query row (arith = 1, Nq = 1, one query batch per unit): the [CLS]-only last layer of the
+// parity mode's pair stack, whose self-attention gives every pair its own keys (its padded caption, kv_len) and one query row.
+// attn_split_kernel would run a 4-wave workgroup of 128 virtual rows for that one row; here one wave serves one (row, head).
+// Lane = d: every key / value row is one coalesced 256-byte read; the score of key j is the wave sum of the same three
+// products the MFMA form accumulates (k_lo.q_hi + k_hi.q_lo + k_hi.q_hi — each exact in f32, 16-bit x 16-bit), P.V likewise
+// (v_lo.p_hi + v_hi.p_lo + v_hi.p_hi).  Keys in chunks of 64 (lane j holds the score of key k0 + j), online softmax across chunks.
+template <typename T16>
+__global__ __launch_bounds__(256) void attn_split_row1_kernel(const AttnF32P p) {
+  const int lane = threadIdx.x & 63;
+  const int z = blockIdx.x * 4 + (threadIdx.x >> 6);     // unit = query batch (units == Bq in this form)
+  const int h = blockIdx.y;
+  if (z >= p.Bq) return;
+  int bk, first, count;
+  resolve_unit(p, z, bk, first, count);
+  const RowInfo ri = row_info(p, 0, first, 1);
+  const float qv = p.q[(size_t)ri.qb * p.ldq + p.q_off + h * 64 + lane] * p.scale;
+  const T16 qh16 = Elt<T16>::from_f32(qv);
+  const float qh = (float)qh16, ql = (float)Elt<T16>::from_f32(qv - qh);
+  const float* kg = p.k + (size_t)bk * p.kv_rows * p.ldk + p.k_off + h * 64 + lane;
+  const float* vg = p.v + (size_t)bk * p.kv_rows * p.ldv + p.v_off + h * 64 + lane;
+  float m = -INFINITY, l = 0.f, acc = 0.f;
+  for (int k0 = 0; k0 < ri.klim; k0 += 64) {
+    const int n = min(64, ri.klim - k0);
+    float s = -INFINITY;                                 // score of key k0 + lane
+#pragma unroll 4
+    for (int j = 0; j < n; ++j) {
+      const float kv = kg[(size_t)(k0 + j) * p.ldk];
+      const T16 kh16 = Elt<T16>::from_f32(kv);
+      const float kh = (float)kh16, kl = (float)Elt<T16>::from_f32(kv - kh);
+      float t = kl * qh;
+      t = __builtin_fmaf(kh, ql, t);
+      t = __builtin_fmaf(kh, qh, t);
+      t = wave_sum(t);
+      if (lane == j) s = t;
+    }
+    const float mn = fmaxf(m, wave_max(s));              // (finite: the chunk holds at least one key)
+    const float alpha = __builtin_amdgcn_exp2f((m - mn) * kLog2e);     // (m == -inf: 0)
+    const float e = __builtin_amdgcn_exp2f((s - mn) * kLog2e);         // (lanes past the chunk: 0)
+    l = l * alpha + wave_sum(e);
+    acc *= alpha;
+    m = mn;
+    const T16 eh16 = Elt<T16>::from_f32(e);
+    const float eh = (float)eh16, el = (float)Elt<T16>::from_f32(e - eh);
+#pragma unroll 4
+    for (int j = 0; j < n; ++j) {
+      const float ph = __shfl(eh, j, 64), pl = __shfl(el, j, 64);
+      const float vv = vg[(size_t)(k0 + j) * p.ldv];
+      const T16 vh16 = Elt<T16>::from_f32(vv);
+      const float vh = (float)vh16, vl = (float)Elt<T16>::from_f32(vv - vh);
+      acc = __builtin_fmaf(vl, ph, acc);
+      acc = __builtin_fmaf(vh, pl, acc);
+      acc = __builtin_fmaf(vh, ph, acc);
+    }
+  }
+  const float inv = l > 0.f ? 1.0f / l : 0.f;
+  store_f32_row<T16>(p, (size_t)ri.qb * p.Nq + ri.t, h, lane, acc * inv);
+}
+
 template <typename T16>
 __global__ __launch_bounds__(256) void attn_f32_arena_kernel(const AttnF32P p) {
   const int lane = threadIdx.x & 63;
@@ -1962,6 +2020,14 @@ extern "C" int vidil_attention_f32(const vidil_attn_f32_args* a, void* stream) {
     });
   }
   VIDIL_REQUIRE(a->kv16 == 0, "attention_f32: kv16 needs arith == 1");
+  if (a->arith == 1 && max_rows == 1 && a->group_start == nullptr) {
+    // split-operand form, one query row per unit (the [CLS]-only last layer of the parity pair stack): one wave per (row, head)
+    const dim3 grid1((units + 3) / 4, a->H);
+    if (bf) hipLaunchKernelGGL(attn_split_row1_kernel<bf16>, grid1, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(attn_split_row1_kernel<f16>, grid1, dim3(256), 0, s, p);
+    VIDIL_CHECK_LAUNCH("attention_f32 (split, one row per unit)");
+    return VIDIL_OK;
+  }
   if (a->arith == 1) {
     // split-operand form on f32 Q / K / V in place: any number of rows per unit (a unit of a few rows leaves three of the four
     // waves without rows: they still stage)

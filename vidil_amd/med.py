@@ -354,7 +354,7 @@ class BertModel(PackedCache, nn.Module):
             if self_done_first or stop_after_self or n_layers is not None:
                 raise K.VidilHipError("run_layers: the parity precision mode runs whole stacks (the caption decoder, "
                                       "BertModel.encode); encode_cls' split schedules are not built for it — BLIP_ITM.itm_pairs "
-                                      "takes the encode() route in that mode")
+                                      "takes encode_cls_parity (or the encode() route) in that mode")
             return self._run_layers_parity(p, h32, h16, rows=rows, T=T, self_k=self_k, self_vt=self_vt, t_off=t_off,
                                            Tk_cap=Tk_cap, NPs=NPs, causal=causal, kv_len=kv_len, cross=cross,
                                            cross_index=cross_index, cross_group=cross_group, cross_groups=cross_groups,
@@ -438,10 +438,12 @@ class BertModel(PackedCache, nn.Module):
         return [(b0, min(B, b0 + n)) for b0 in range(0, B, n)]
 
     def _run_layers_parity(self, p, h32, h3, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len, cross, cross_index,
-                           cross_group, cross_groups, cross_max_group, ws, arena, arena_slot_stride):
+                           cross_group, cross_groups, cross_max_group, ws, arena, arena_slot_stride, n_layers=None):
         """run_layers in the parity precision mode: ``h3`` [rows*T, 3C] carries the hidden states as [hi | lo | hi]
         operand rows, every GEMM runs against [W_hi | W_hi | W_lo] with K tripled, LayerNorm / attention write split rows
-        directly and the GELU output goes through f32 + vidil_split3_f32.  Same launch sequence otherwise."""
+        directly and the GELU output goes through f32 + vidil_split3_f32.  Same launch sequence otherwise.
+        n_layers: only the first n layers (encode_cls_parity runs the last itself); ws["planes_h"] then tells it how many
+        planes of ``h3`` the last of them wrote."""
         cfg = self.config
         H, C = cfg.num_attention_heads, cfg.hidden_size
         eps = cfg.layer_norm_eps
@@ -477,6 +479,7 @@ class BertModel(PackedCache, nn.Module):
             planes_h = 2
         K.poison_third_plane(planes, inter3)
         K.poison_third_plane(planes_h, o3, h3)
+        ws["planes_h"] = planes_h
         Nk = t_off + T
         if arena is not None and T > 1 and t_off != 0:
             raise K.VidilHipError("run_layers: a multi-token block can only be appended to a beam arena at position 0")
@@ -495,7 +498,7 @@ class BertModel(PackedCache, nn.Module):
                 #  prompt pass; a longer prompt x group must be built with the f32-row cross K|V instead)
                 raise K.VidilHipError(f"run_layers (parity mode, split attention): {T} tokens x {cross_group} sequences per image exceed the 32 "
                                       "query rows per image the 16-bit cross K/V tiles serve — build the session with tiled_cross=False")
-        for i, d in enumerate(p["layers"]):
+        for i, d in enumerate(p["layers"][:n_layers]):
             if f32_attn:
                 K.gemm(h3, d["qkv_w3"], d["qkv_b"], out=qkv32, split_k=True, a_planes=planes_h)
                 if arena is not None and T == 1:
@@ -783,6 +786,61 @@ class BertModel(PackedCache, nn.Module):
         K.gemm(inter, d["o_w"], d["o_b"], out=tmp, resid=c32)
         K.layernorm(tmp, d["o_g"], d["o_bt"], eps, out16=c16, out32=c32)
         return c32, c16
+
+    def cls_last_parity_ok(self, cross):
+        """encode_cls_parity serves this model and these cross K / V: the parity mode with an f32-row attention kind (cross K | V
+        as f32 rows: project_cross_kv's parity form) and more than one layer."""
+        return (self.parity and parity_attention_f32(self) and self.config.num_hidden_layers > 1
+                and (cross is None or getattr(cross, "f32", False)))
+
+    def encode_cls_parity(self, ids_i32, kv_len_i32, cross: CrossKV, cross_index=None, cross_groups=None, cross_max_group=0):
+        """encode_cls in the parity precision mode (f32-row attention kinds; cls_last_parity_ok): layers 0..L-2 on every token
+        (_run_layers_parity), the last layer's keys / values of the self-attention over every token, and everything else of that
+        layer — the query, both attentions, the three dense + LayerNorm blocks and the feed-forward — on the P [CLS] rows alone.
+        Same operands per [CLS] row as encode(); the one-row self-attention is vidil_attention_f32's one-row-per-unit form.
+        Returns (c32 f32 [P, C], c3 [P, 3C] = its [hi | lo | hi] rows)."""
+        require_cuda(ids_i32, "BertModel.encode_cls_parity")
+        if not self.cls_last_parity_ok(cross):
+            raise K.VidilHipError("encode_cls_parity: needs the parity mode with the 'split' or 'f32' attention kind, more than one "
+                                  "layer and f32-row cross K | V (project_cross_kv in the same mode)")
+        p = self.packed()
+        cfg = self.config
+        P, T = ids_i32.shape
+        H, C, L = cfg.num_attention_heads, cfg.hidden_size, cfg.num_hidden_layers
+        eps = cfg.layer_norm_eps
+        dev = ids_i32.device
+        arith = parity_attention_arith(self)
+        h32, h3 = self.embed(ids_i32.reshape(-1), T, 0)
+        cdt = h3.dtype
+        ws = {}
+        self._run_layers_parity(p, h32, h3, rows=P, T=T, self_k=None, self_vt=None, t_off=0, Tk_cap=T, NPs=0, causal=False,
+                                kv_len=kv_len_i32, cross=cross, cross_index=cross_index, cross_group=1, cross_groups=cross_groups,
+                                cross_max_group=cross_max_group, ws=ws, arena=None, arena_slot_stride=1, n_layers=L - 1)
+        planes_h = ws["planes_h"]            # (planes of h3 the last LayerNorm wrote; the [CLS] side below writes all three)
+        d = p["layers"][L - 1]
+        kv32 = torch.empty((P * T, 2 * C), dtype=torch.float32, device=dev)
+        K.gemm(h3, d["qkv_w3"][C:], d["qkv_b"][C:], out=kv32, split_k=True, a_planes=planes_h)
+        c32 = h32.view(P, T, C)[:, 0].contiguous()
+        c3 = h3.view(P, T, 3 * C)[:, 0].contiguous()
+        q32 = torch.empty((P, C), dtype=torch.float32, device=dev)
+        o3 = torch.empty((P, 3 * C), dtype=cdt, device=dev)
+        tmp = torch.empty((P, C), dtype=torch.float32, device=dev)
+        K.gemm(c3, d["qkv_w3"][:C], d["qkv_b"][:C], out=q32, split_k=True, a_planes=planes_h)
+        K.attention_f32(q32, kv32[:, :C], kv32[:, C:], o3, Bq=P, H=H, Nq=1, Nk=T, kv_rows=T, kv_len=kv_len_i32, arith=arith)
+        K.gemm(o3, d["ao_w3"], d["ao_b"], out=tmp, resid=c32, split_k=True)
+        K.layernorm(tmp, d["ao_g"], d["ao_bt"], eps, out16=c3, out32=c32, split3=True)
+        if cross is not None:
+            K.gemm(c3, d["cq_w3"], d["cq_b"], out=q32, split_k=True)
+            kv = cross.k[L - 1]                                     # f32 [B, Te, 2C]: keys | values
+            K.attention_f32(q32, kv[..., :C], kv[..., C:], o3, Bq=P, H=H, Nq=1, Nk=cross.Te, kv_rows=cross.Te, kv_index=cross_index,
+                            group_start=cross_groups, max_group=cross_max_group, arith=arith)
+            K.gemm(o3, d["co_w3"], d["co_b"], out=tmp, resid=c32, split_k=True)
+            K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=c3, out32=c32, split3=True)
+        inter3 = torch.empty((P, 3 * cfg.intermediate_size), dtype=cdt, device=dev)
+        K.gemm(c3, d["i_w3"], d["i_b"], split3_out=inter3, act=K.ACT_GELU_ERF, split_k=True)
+        K.gemm(inter3, d["o_w3"], d["o_b"], out=tmp, resid=c32, split_k=True)
+        K.layernorm(tmp, d["o_g"], d["o_bt"], eps, out16=c3, out32=c32, split3=True)
+        return c32, c3
 
     def forward(self, *a, **k):
         raise NotImplementedError("use BertModel.encode / BLIP_ITM on the hot path")
