@@ -387,6 +387,23 @@ int vidil_logsoftmax_topk(const float* logits, const float* beam_scores,
 /* ids of the row's sequence seqs[(b*nb+beam)*ld_seqs ..] (prompt included):       */
 /*   lp[t] = lp[t] < 0 ? lp[t] * penalty : lp[t] / penalty   (f32, once per token) */
 /* before the ban (MinLength) and the beam score are applied.  cur_len <= 64.      */
+/*                                                                                 */
+/* nb == 0: the TEACHER-FORCED form — no search, score the given token (reference: */
+/* models/med.py:909-917, the cross-entropy of BertLMHeadModel.forward(labels=...)).*/
+/* Per row r of logits f32 [B, V] (B = number of rows):                            */
+/*   label = seqs[r * ld_seqs]            (ld_seqs >= 1; label < 0 means "ignore") */
+/*   lp    = log_softmax(logits[r])       (f32, ONE pass over the row: running     */
+/*                                         max, rescaled sum of exp, sum of logits)*/
+/*   out_scores[2r]   = lp[label]                     (0 for an ignored row)       */
+/*   out_scores[2r+1] = (1/V) * sum_j lp[j]           (= mean logit - lse: the     */
+/*                      label-smoothing term; 0 for an ignored row)                */
+/*   out_index[r]     = argmax_j logits[r][j]         (lowest index on ties;       */
+/*                      written for EVERY row, ignored ones included)              */
+/* out_scores f32 [B, 2], out_index i32 [B].  beam_scores, beams_in_logits,        */
+/* ban_token, cur_len and penalty are not read in this form (pass NULL, 0, -1, 0,  */
+/* 1.0).  A label >= V is an argument error, but labels live in device memory and   */
+/* the host cannot see them: the kernel treats such a row as ignored.  -inf logits  */
+/* are allowed (they carry probability 0; lp[label] stays finite, the mean is -inf).*/
 int vidil_logsoftmax_topk_penalty(const float* logits, const float* beam_scores,
                                   int32_t B, int32_t nb, int32_t beams_in_logits,
                                   int32_t V, int32_t ban_token, const int32_t* seqs,

@@ -25,6 +25,7 @@ _DEFAULT_MED_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)   # run_video_CapFilt.py:133
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+CAPTION_MAX_LENGTH = 40                           # models/blip.py:109 (captions given to forward are cut to 40 tokens)
 
 
 def resolve_med_config(path):
@@ -81,6 +82,7 @@ class DecodeTrace:
         self.logits = []       # f32 [R,V] per forward
         self.cand_scores = []
         self.cand_index = []
+        self.scores = None     # f32 [B]: the winning hypothesis' score (sum of log-probabilities / length) as the search reports it
 
 
 class DecoderSession:
@@ -454,7 +456,9 @@ class BLIP_Decoder(nn.Module):
                 unit(cur_len)
             cur_len += 1
             yield
-        out_tok, out_len, _ = K.beam_finalize(cur["bufs"], cur_len, eos, pad)
+        out_tok, out_len, out_score = K.beam_finalize(cur["bufs"], cur_len, eos, pad)
+        if trace is not None:
+            trace.scores = out_score          # (a traced search never compacts: one score per image)
         if final_tok is None:
             return out_tok, out_len
         final_tok[orig] = out_tok[:orig.numel()]
@@ -520,8 +524,57 @@ class BLIP_Decoder(nn.Module):
                                        min_length=min_length, repetition_penalty=repetition_penalty)
         return self.decode_captions(out_tok)
 
+    # ------------------------------------------------------------------ scoring given captions
+    def tokenize_captions(self, captions):
+        """models/blip.py:109-111: padding='longest', truncation at CAPTION_MAX_LENGTH tokens, first id := [DEC].
+        Returns (ids i32 [P, T], lens i32 [P]) on the host."""
+        enc = self.tokenizer(list(captions), padding="longest", truncation=True, max_length=CAPTION_MAX_LENGTH, return_tensors="pt")
+        ids = enc.input_ids.clone()
+        ids[:, 0] = self.tokenizer.bos_token_id
+        return ids.to(torch.int32), enc.attention_mask.sum(dim=1).to(torch.int32)
+
+    @torch.no_grad()
+    def caption_nll(self, image_or_enc16, captions, image_index=None, *, group_start=None, add_prompt=False,
+                    label_smoothing=0.1, reduction="none"):
+        """How likely the captioner finds GIVEN captions: the teacher-forced loss of models/blip.py:104-125.
+
+        image_or_enc16: images f32 [B,3,S,S] on the GPU (the ViT runs once per image), or their image tokens as the ViT
+        left them — [B, Te, width], or [B*Te, width] for this model's ViT (``forward_both``'s second result).  Caption p
+        describes image ``image_index[p]`` (default: image p), or, in image-major order, image j owns captions
+        group_start[j] .. group_start[j+1]-1.  As in the reference the strings contain the prompt; add_prompt=True
+        prepends it.  The first ``prompt_length`` tokens are not scored; the closing [SEP] is.
+        reduction='none': (loss f32 [P] summed per caption — models/med.py:916-917 —, target-token counts i32 [P]); a caption
+        that truncates to no target token scores 0 with count 0.  reduction='mean': the 0-dim f32 mean over all target tokens
+        (what ``forward`` returns).  label_smoothing=0.0 gives plain negative log-likelihood sums."""
+        if reduction not in ("none", "mean"):
+            raise ValueError(f"caption_nll: reduction={reduction!r} (none | mean)")
+        x = image_or_enc16
+        require_cuda(x, "BLIP_Decoder.caption_nll")
+        if x.dim() == 4:
+            B = x.shape[0]
+            _, enc16 = self.visual_encoder.forward_both(x)
+        elif x.dim() == 3:
+            B, enc16 = x.shape[0], x.reshape(-1, x.shape[-1])
+        elif x.dim() == 2:
+            Te = self.visual_encoder.patch_embed.num_patches + 1
+            if x.shape[0] % Te:
+                raise ValueError(f"caption_nll: {x.shape[0]} image-token rows are not a multiple of this ViT's {Te} tokens per image")
+            B, enc16 = x.shape[0] // Te, x
+        else:
+            raise ValueError(f"caption_nll: images [B,3,S,S] or image tokens [B,Te,width] / [B*Te,width] expected, got {tuple(x.shape)}")
+        captions = [self.prompt + c for c in captions] if add_prompt else list(captions)
+        ids, lens = self.tokenize_captions(captions)
+        res = self.text_decoder.score(enc16.contiguous(), B, ids, lens, image_index=image_index, group_start=group_start,
+                                      label_smoothing=label_smoothing, prompt_length=self.prompt_length)
+        if reduction == "none":
+            return res.loss_sum, res.count
+        return (res.token_loss.double().sum() / max(1, res.token_loss.numel())).float()
+
+    @torch.no_grad()
     def forward(self, image, caption):
-        raise NotImplementedError("training loss is out of scope (inference hot path only)")
+        """Reference: models/blip.py:104-125 — the label-smoothed (0.1) language-model loss of the given captions, one per
+        image, averaged over their target tokens.  Returns a 0-dim f32 tensor on the device (no backward pass)."""
+        return self.caption_nll(image, caption, label_smoothing=0.1, reduction="mean")
 
 
 def blip_decoder(pretrained="", **kwargs):

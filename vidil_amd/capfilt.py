@@ -49,6 +49,20 @@ def filter_captions(filterer, images, texts, threshold, mode="max_filter"):
     return kept
 
 
+@torch.no_grad()
+def score_captions(captioner, images, texts, label_smoothing=0.0):
+    """The captioner's own likelihood of ``texts`` on every frame, beside the ITM probability of ``filter_captions``:
+    images f32 [F,3,S,S], C texts WITHOUT the prompt (what ``caption_frames`` returns, or original captions) -> f32 [C, F]
+    of negative log-likelihood per scored token (lower: more likely).  The ViT runs once per frame and all C*F pairs go
+    through one teacher-forced pass, image-major (BLIP_Decoder.caption_nll / BertLMHeadModel.score)."""
+    F, texts = images.shape[0], list(texts)
+    C = len(texts)
+    _, y16 = captioner.visual_encoder.forward_both(images)
+    nll, count = captioner.caption_nll(y16.view(F, -1, y16.shape[-1]), texts * F, group_start=torch.arange(F + 1) * C,
+                                       add_prompt=True, label_smoothing=label_smoothing, reduction="none")
+    return (nll / count.clamp(min=1)).view(F, C).t().contiguous()
+
+
 def dedup(captions):
     """run_video_CapFilt.py:185-188."""
     out = []

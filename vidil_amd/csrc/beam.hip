@@ -219,6 +219,98 @@ __global__ __launch_bounds__(256) void lsm_topk_kernel(const float* __restrict__
   }
 }
 
+// ---- teacher-forced form (vidil_logsoftmax_topk_penalty with num_beams == 0): no search, score the GIVEN token of every row
+// (reference: models/med.py:909-917, CrossEntropyLoss(label_smoothing) on the shifted prediction scores).  One workgroup per
+// row, ONE read of the row: every thread keeps an online-softmax state (running maximum m, sum of exp(x - m)), the plain sum
+// of its logits (the label-smoothing term needs mean_j lp[j] = mean logit - lse) and its best (logit, index); the states are
+// combined as (max, sum) pairs by wave shuffles and one LDS exchange.  Rows start 4-byte aligned only (V = 30,524: odd rows
+// are 8 bytes off a 16-byte boundary), so a row is a scalar head up to the next 16-byte boundary, 16-byte loads, a scalar tail.
+// exp(x - m) is formed from the DIFFERENCE (x - m) * log2(e): an -inf logit gives exp2(-inf) = 0, and no term is ever
+// inf - inf because a thread adds nothing while its maximum is still -inf.
+struct TfState {
+  float m, sum, tot, bv;
+  int bi;
+};
+__device__ __forceinline__ void tf_one(TfState& s, float x, int i) {
+  constexpr float L2E = 1.4426950408889634f;
+  if (x > s.m) {
+    s.sum *= __builtin_amdgcn_exp2f((s.m - x) * L2E);
+    s.m = x;
+  }
+  if (s.m > -INFINITY) s.sum += __builtin_amdgcn_exp2f((x - s.m) * L2E);
+  s.tot += x;
+  if (x > s.bv) { s.bv = x; s.bi = i; }            // (indices arrive in increasing order: the first of equals stays)
+}
+__device__ __forceinline__ void tf_four(TfState& s, const f32x4 x, int i) {
+  constexpr float L2E = 1.4426950408889634f;
+  const float mx = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
+  if (mx > s.m) {
+    s.sum *= __builtin_amdgcn_exp2f((s.m - mx) * L2E);
+    s.m = mx;
+  }
+  if (s.m > -INFINITY)
+    s.sum += (__builtin_amdgcn_exp2f((x[0] - s.m) * L2E) + __builtin_amdgcn_exp2f((x[1] - s.m) * L2E)) +
+             (__builtin_amdgcn_exp2f((x[2] - s.m) * L2E) + __builtin_amdgcn_exp2f((x[3] - s.m) * L2E));
+  s.tot += (x[0] + x[1]) + (x[2] + x[3]);
+  if (mx > s.bv) {                                 // rare after the first few loads: a thread's best moves O(log n) times
+    s.bv = mx;
+    s.bi = i + (x[0] == mx ? 0 : x[1] == mx ? 1 : x[2] == mx ? 2 : 3);
+  }
+}
+
+__global__ __launch_bounds__(256) void tf_logprob_kernel(const float* __restrict__ logits, int V,
+                                                         const int32_t* __restrict__ labels, int ld_labels,
+                                                         float* __restrict__ out_s, int* __restrict__ out_i) {
+  __shared__ float red_m[4], red_s[4], red_t[4];
+  __shared__ Cand red_b[4];
+  const int tid = threadIdx.x;
+  const size_t r = blockIdx.x;
+  const float* row = logits + r * (size_t)V;
+  TfState s{-INFINITY, 0.f, 0.f, -INFINITY, 0x7fffffff};
+  int head = (int)(((16u - (unsigned)((uintptr_t)row & 15u)) & 15u) >> 2);   // elements before the first 16-byte boundary
+  if (head > V) head = V;
+  const int nvec = (V - head) >> 2;
+  const int tail0 = head + nvec * 4;
+  // (a thread's indices must arrive in increasing order for the tie rule: head, then its vectors, then the tail)
+  if (tid < head) tf_one(s, row[tid], tid);
+  const f32x4* rv = (const f32x4*)(row + head);
+#pragma unroll 2
+  for (int v = tid; v < nvec; v += 256) tf_four(s, rv[v], head + v * 4);
+  if (tid < V - tail0) tf_one(s, row[tail0 + tid], tail0 + tid);
+
+  // ---- the block's (max, sum) pair, total and best element: shuffles inside a wave, one LDS exchange across the four
+  const float wm = wave_max(s.m);
+  constexpr float L2E = 1.4426950408889634f;
+  const float ws = wave_sum(s.m == -INFINITY ? 0.f : s.sum * __builtin_amdgcn_exp2f((s.m - wm) * L2E));
+  const float wt = wave_sum(s.tot);
+  Cand c{s.bv, s.bi};
+  c = wave_best(c);
+  if ((tid & 63) == 0) {
+    red_m[tid >> 6] = wm; red_s[tid >> 6] = ws; red_t[tid >> 6] = wt; red_b[tid >> 6] = c;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  const float M = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+  float sum = 0.f, tot = 0.f;
+  Cand g = red_b[0];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    if (red_m[w] > -INFINITY) sum += red_s[w] * __builtin_amdgcn_exp2f((red_m[w] - M) * L2E);
+    tot += red_t[w];
+    if (w > 0 && better(red_b[w].s, red_b[w].i, g.s, g.i)) g = red_b[w];
+  }
+  out_i[r] = g.i == 0x7fffffff ? 0 : g.i;          // (a row of -inf only has no maximum: index 0)
+  const int label = labels[r * (size_t)ld_labels];
+  float lp = 0.f, lp_mean = 0.f;
+  if (label >= 0 && label < V) {                   // (label < 0: ignored; label >= V cannot be refused by the host: ignored too)
+    const float lse = logf(sum);
+    lp = (row[label] - M) - lse;
+    lp_mean = (tot / (float)V - M) - lse;
+  }
+  out_s[2 * r] = lp;
+  out_s[2 * r + 1] = lp_mean;
+}
+
 // ---- BeamHypotheses.add (double arithmetic: the reference does this on Python floats)
 __device__ void hyp_add(const vidil_beam_state& st, int b, int nb, int max_len, const int32_t* toks, int len,
                         double sum_logprobs) {
@@ -358,6 +450,18 @@ extern "C" int vidil_logsoftmax_topk_penalty(const float* logits, const float* b
                                              int32_t beams_in_logits, int32_t V, int32_t ban_token, const int32_t* seqs,
                                              int32_t cur_len, int32_t ld_seqs, float penalty, float* out_scores,
                                              int32_t* out_index, void* stream) {
+  if (nb == 0) {
+    // teacher-forced form: seqs holds one label per row (row stride ld_seqs); beam_scores, beams_in_logits, ban_token,
+    // cur_len and penalty are not read
+    VIDIL_REQUIRE(seqs != nullptr, "logsoftmax_topk_penalty (num_beams=0, teacher-forced): null labels (seqs)");
+    VIDIL_REQUIRE(logits && out_scores && out_index, "logsoftmax_topk_penalty (num_beams=0, teacher-forced): null pointer");
+    VIDIL_REQUIRE(B > 0 && V > 0, "logsoftmax_topk_penalty (num_beams=0, teacher-forced): bad shape rows=%d V=%d", B, V);
+    VIDIL_REQUIRE(ld_seqs >= 1, "logsoftmax_topk_penalty (num_beams=0, teacher-forced): ld_seqs=%d must be >= 1", ld_seqs);
+    hipLaunchKernelGGL(tf_logprob_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, V, seqs, ld_seqs, out_scores,
+                       out_index);
+    VIDIL_CHECK_LAUNCH("logsoftmax_topk_penalty (teacher-forced)");
+    return VIDIL_OK;
+  }
   VIDIL_REQUIRE(seqs != nullptr, "logsoftmax_topk_penalty: null sequences");
   VIDIL_REQUIRE(cur_len >= 1 && cur_len <= MAXLEN && ld_seqs >= cur_len,
                 "logsoftmax_topk_penalty: cur_len=%d must be in [1, %d] and <= ld_seqs=%d", cur_len, MAXLEN, ld_seqs);

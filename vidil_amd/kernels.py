@@ -17,7 +17,7 @@ from ._lib import (ACT_GELU_ERF, ACT_NONE, ACT_QUICK_GELU, DT_BF16, DT_F16, DT_F
 
 __all__ = [
     "gemm", "layernorm", "attention", "patchify_f32", "patchify_u8", "set_cls_row",
-    "embed_tokens", "gather_rows", "l2_normalize_rows", "logsoftmax_topk", "BeamBuffers",
+    "embed_tokens", "gather_rows", "l2_normalize_rows", "logsoftmax_topk", "token_logprobs", "BeamBuffers",
     "beam_update", "beam_finalize", "scan_topk", "scan_topk_ws_bytes",
     "ACT_NONE", "ACT_GELU_ERF", "ACT_QUICK_GELU", "VidilHipError",
 ]
@@ -463,6 +463,29 @@ def logsoftmax_topk(logits, beam_scores, B, nb, ban_token=-1, out_scores=None, o
                                             ban_token, _ptr(out_scores, torch.float32), _ptr(out_index, torch.int32),
                                             _stream()), "logsoftmax_topk")
     return out_scores, out_index
+
+
+def token_logprobs(logits, labels, out_scores=None, out_index=None):
+    """Teacher-forced scoring of given tokens (vidil_logsoftmax_topk_penalty with num_beams == 0; reference:
+    models/med.py:909-917): logits f32 [R, V], labels i32 [R] (< 0: ignored row) ->
+    (lp_label f32 [R] = log_softmax(logits[r])[labels[r]], lp_mean f32 [R] = mean_j log_softmax(logits[r])[j] — the
+    label-smoothing term —, argmax i32 [R], lowest index on ties).  Ignored rows score exactly 0 in both; their argmax is
+    still written.  One read of the logits."""
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+        raise VidilHipError(f"token_logprobs: logits [R, V] and labels [R] expected, got {tuple(logits.shape)} / {tuple(labels.shape)}")
+    R, V = logits.shape
+    dev = logits.device
+    if out_scores is None:
+        out_scores = torch.empty((R, 2), dtype=torch.float32, device=dev)
+    if out_index is None:
+        out_index = torch.empty((R,), dtype=torch.int32, device=dev)
+    if R:
+        check(_lib.load().vidil_logsoftmax_topk_penalty(_ptr(logits, torch.float32, "token_logprobs.logits"), None, R, 0, 0, V, -1,
+                                                        _ptr(labels, torch.int32, "token_logprobs.labels"), 0, 1, 1.0,
+                                                        _ptr(out_scores, torch.float32, "token_logprobs.out_scores"),
+                                                        _ptr(out_index, torch.int32, "token_logprobs.out_index"), _stream()),
+              "token_logprobs")
+    return out_scores[:, 0], out_scores[:, 1], out_index
 
 
 class BeamBuffers:

@@ -26,6 +26,50 @@ from .packing import FP8, PackedCache, fold_layernorm, parity_attention_arith, p
 
 LN_EPS_DEFAULT = 1e-12
 
+#: f32 logits BertLMHeadModel.score holds at a time: the target rows go through the LM head and the one-pass reduction
+#: (kernels.token_logprobs) in row blocks of this many bytes, in ONE reused buffer (8,704 rows of 30,524 logits)
+LOGITS_BLOCK_BYTES = 1 << 30
+#: rows of EVERY vocabulary-GEMM launch of lm_logits_rows (a shorter tail is padded with a repeated row): with M fixed the
+#: library's GEMM dispatch picks the same kernel for every launch, so a caption's logits cannot depend on what shares its batch
+HEAD_GEMM_ROWS = 512
+#: shortest token block score() runs the decoder stack on (shorter batches are right-padded): above 32 query rows per unit
+#: every attention launch of the stack is served by the staged kernel whatever the longest caption of the batch is
+SCORE_MIN_TOKENS = 33
+#: captions per stack pass of score() when captions map to images through image_index (one attention unit per caption)
+SCORE_MAX_CAPTIONS_PER_PASS = 16384
+
+
+def teacher_forced_targets(ids, lens, prompt_length):
+    """The labels of the teacher-forced caption loss as a pure function (models/blip.py:113-114 and the shift of
+    models/med.py:912-913): ids int [P, T] right-padded, lens int [P] real tokens per row -> int64 [P, T] with
+    out[p, t] = ids[p, t + 1] where position t + 1 is a real token past the prompt, -100 (ignored) elsewhere —
+    the logits at position t are scored against the token at t + 1."""
+    ids = torch.as_tensor(ids).long()
+    lens = torch.as_tensor(lens).long().to(ids.device)
+    T = ids.shape[1]
+    t = torch.arange(T, device=ids.device)
+    tgt = torch.where(t[None, :] < lens[:, None], ids, torch.full_like(ids, -100))
+    tgt[:, :prompt_length] = -100
+    out = torch.full_like(tgt, -100)
+    out[:, :-1] = tgt[:, 1:]
+    return out
+
+
+class CaptionScores:
+    """Result of BertLMHeadModel.score.  Per caption: ``loss_sum`` f32 [P] (the label-smoothed loss summed over the caption's
+    target tokens, models/med.py:916-917) and ``count`` i32 [P].  Per target token, N in all, in the order scored:
+    ``lp_label`` / ``lp_mean`` f32 [N] (log-probability of the given token, mean log-probability over the vocabulary),
+    ``argmax`` i32 [N] (the greedy token at that position), ``token_loss`` f32 [N], ``caption`` / ``position`` int64 [N]
+    (caption index and position of the TARGET token in it)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def tokens_of(self, p):
+        """Indices (int64, device) of caption p's target tokens, in position order."""
+        idx = (self.caption == p).nonzero().view(-1)
+        return idx[self.position[idx].argsort()]
+
 
 class BertConfig:
     """The fields of configs/med_config.json the hot path reads."""
@@ -935,5 +979,185 @@ class BertLMHeadModel(PackedCache, nn.Module):
         K.gemm(t16, p["dec_w"], p["dec_b"], out=out)
         return out
 
+    def lm_logits_rows(self, h16, row_index, out=None, h32=None):
+        """LM head on an arbitrary list of hidden-state rows: row_index int [n] (device) into h16 [M, C] (h32 [M, C] for the
+        error-compensated head) -> f32 [n, V].  The rows are gathered first, then the same two GEMMs and LayerNorm as
+        ``lm_logits`` run on them; the vocabulary GEMM is issued HEAD_GEMM_ROWS rows at a time, always that many (the tail is
+        padded with a repeated row), so every launch is the same kernel whatever n is.
+        out: an f32 buffer of at least ceil(n / HEAD_GEMM_ROWS) * HEAD_GEMM_ROWS rows of V to write into (the result is its
+        first n rows)."""
+        p = self.packed()
+        cfg = self.config
+        C, V, G = cfg.hidden_size, cfg.vocab_size, HEAD_GEMM_ROWS
+        dev, cdt = h16.device, h16.dtype
+        n = row_index.numel()
+        n_pad = (n + G - 1) // G * G
+        if out is None:
+            out = torch.empty((n_pad, V), dtype=torch.float32, device=dev)
+        elif out.dim() != 2 or out.shape[0] < n_pad or out.shape[1] != V or out.dtype != torch.float32 or not out.is_contiguous():
+            raise K.VidilHipError(f"lm_logits_rows: out must be a contiguous f32 [>= {n_pad}, {V}] buffer, got {out.dtype} {tuple(out.shape)}")
+        if n == 0:
+            return out[:0]
+        idx = row_index.to(torch.int64)
+        if n_pad != n:
+            idx = torch.cat([idx, idx[:1].expand(n_pad - n)])
+        t32 = torch.empty((n_pad, C), dtype=torch.float32, device=dev)
+        if p["precise"]:
+            if h32 is None:
+                raise K.VidilHipError("lm_logits_rows: the error-compensated head (precise_head / parity mode) needs the f32 hidden states")
+            a3 = K.split3(h32.index_select(0, idx), torch.empty((n_pad, 3 * C), dtype=cdt, device=dev))
+            K.gemm(a3, p["t_w3"], p["t_b"], out=t32, act=K.ACT_GELU_ERF, split_k=True)
+            tn32 = torch.empty((n_pad, C), dtype=torch.float32, device=dev)
+            K.layernorm(t32, p["t_g"], p["t_bt"], cfg.layer_norm_eps, out32=tn32)
+            K.split3(tn32, a3)
+            for r0 in range(0, n_pad, G):
+                K.gemm(a3[r0:r0 + G], p["dec_w3"], p["dec_b"], out=out[r0:r0 + G], split_k=True)
+            return out[:n]
+        K.gemm(h16.index_select(0, idx), p["t_w"], p["t_b"], out=t32, act=K.ACT_GELU_ERF)
+        t16 = torch.empty((n_pad, C), dtype=cdt, device=dev)
+        K.layernorm(t32, p["t_g"], p["t_bt"], cfg.layer_norm_eps, out16=t16)
+        for r0 in range(0, n_pad, G):
+            K.gemm(t16[r0:r0 + G], p["dec_w"], p["dec_b"], out=out[r0:r0 + G])
+        return out[:n]
+
+    @torch.no_grad()
+    def score(self, enc16, B, ids, lens, *, image_index=None, group_start=None, max_group=0, label_smoothing=0.1,
+              prompt_length):
+        """Teacher-forced scores of GIVEN captions (models/med.py:886-917 with labels; models/blip.py:104-125 builds them).
+
+        enc16: image tokens of B images, 16-bit [B*Te, width] ([hi | lo | hi] rows in the parity mode).  ids int [P, T]
+        right-padded caption ids ([DEC] first), lens int [P].  Caption p describes image ``image_index[p]`` (any order;
+        default: image p), or — IMAGE-MAJOR caption order — image j owns captions group_start[j] .. group_start[j+1]-1
+        (at most max_group each; 0: taken from the table).  The logits at position t are scored against token t + 1 for
+        prompt_length - 1 <= t <= lens - 2 (``teacher_forced_targets``); a caption's loss is the sum over its targets of
+        (1 - eps) * (-lp[label]) + eps * (-mean_j lp[j]), eps = label_smoothing.  Returns a ``CaptionScores``.
+
+        Schedule: one causal pass over blocks of T = max(lens) tokens (at least SCORE_MIN_TOKENS) per caption — no KV arena,
+        the right padding is hidden by the causal mask —, the stack a DecoderSession runs (LN-folded / parity); cross K/V
+        and the stack over at most BertModel.MAX_IMAGES_PER_LAUNCH images at a time; the LM head on the target rows only,
+        in row blocks of LOGITS_BLOCK_BYTES of logits that one kernel reduces in one read (kernels.token_logprobs)."""
+        require_cuda(enc16, "BertLMHeadModel.score")
+        bert, cfg = self.bert, self.config
+        dev = enc16.device
+        V, H, L = cfg.vocab_size, cfg.num_attention_heads, cfg.num_hidden_layers
+        eps_ls = float(label_smoothing)
+        if not 0.0 <= eps_ls < 1.0:
+            raise ValueError(f"score: label_smoothing={label_smoothing} must be in [0, 1)")
+        ids_c = torch.as_tensor(ids).cpu().long()
+        lens_c = torch.as_tensor(lens).cpu().long().view(-1)
+        if ids_c.dim() != 2 or lens_c.numel() != ids_c.shape[0]:
+            raise ValueError(f"score: ids [P, T] and lens [P] expected, got {tuple(ids_c.shape)} / {tuple(lens_c.shape)}")
+        P, Tin = ids_c.shape
+        if P and (int(lens_c.min()) < 0 or int(lens_c.max()) > Tin):
+            raise ValueError(f"score: lens must be in [0, {Tin}]")
+        if B <= 0 or enc16.shape[0] % B:
+            raise ValueError(f"score: {enc16.shape[0]} image-token rows do not divide into B={B} images")
+        Te = enc16.shape[0] // B
+        n_img = bert.MAX_IMAGES_PER_LAUNCH
+        # ---- passes: (first image, last image + 1, caption indices, their image within the block | group table, max group)
+        passes = []
+        if group_start is not None:
+            if image_index is not None:
+                raise ValueError("score: image_index and group_start are mutually exclusive")
+            gs = torch.as_tensor(group_start).cpu().long().view(-1)
+            if gs.numel() != B + 1 or int(gs[0]) != 0 or int(gs[-1]) != P or bool((gs[1:] < gs[:-1]).any()):
+                raise ValueError(f"score: group_start must be a non-decreasing table of {B + 1} entries from 0 to {P}")
+            if max_group and int((gs[1:] - gs[:-1]).max()) > max_group:
+                raise ValueError(f"score: a group holds more than max_group={max_group} captions")
+            for b0 in range(0, B, n_img):
+                b1 = min(B, b0 + n_img)
+                p0, p1 = int(gs[b0]), int(gs[b1])
+                if p1 > p0:
+                    g = gs[b0:b1 + 1] - p0
+                    passes.append((b0, b1, torch.arange(p0, p1), None, g, int((g[1:] - g[:-1]).max())))
+        else:
+            if image_index is None:
+                if P != B:
+                    raise ValueError(f"score: {P} captions for {B} images need image_index or group_start")
+                img = torch.arange(P)
+            else:
+                img = torch.as_tensor(image_index).cpu().long().view(-1)
+            if img.numel() != P or (P and (int(img.min()) < 0 or int(img.max()) >= B)):
+                raise ValueError(f"score: image_index must hold {P} entries in [0, {B})")
+            for b0 in range(0, B, n_img):
+                b1 = min(B, b0 + n_img)
+                sel = ((img >= b0) & (img < b1)).nonzero().view(-1)
+                for c0 in range(0, sel.numel(), SCORE_MAX_CAPTIONS_PER_PASS):
+                    s = sel[c0:c0 + SCORE_MAX_CAPTIONS_PER_PASS]
+                    passes.append((b0, b1, s, img[s] - b0, None, 0))
+        labels_all = teacher_forced_targets(ids_c, lens_c, prompt_length)
+        N = int((labels_all >= 0).sum())
+        scores = torch.zeros((N, 2), dtype=torch.float32, device=dev)
+        amax = torch.zeros((N,), dtype=torch.int32, device=dev)
+        caps, poss = [], []
+        block_rows = max(1, LOGITS_BLOCK_BYTES // (4 * V))
+        if block_rows >= HEAD_GEMM_ROWS:
+            block_rows = block_rows // HEAD_GEMM_ROWS * HEAD_GEMM_ROWS
+        buf = None
+        cross, cross_of = None, None
+        done = 0
+        fused = None
+        for b0, b1, s, img_local, g_local, mg in passes:
+            if cross_of != (b0, b1):         # (more than 32 query rows per image in every launch: row-major values)
+                cross = bert.project_cross_kv(enc16[b0 * Te:b1 * Te], b1 - b0, Te, v_rowmajor=True)
+                cross_of = (b0, b1)
+            Pb = s.numel()
+            ln = lens_c[s]
+            T = max(SCORE_MIN_TOKENS, int(ln.max()))
+            if T > cfg.max_position_embeddings:
+                raise ValueError(f"score: {T} tokens exceed max_position_embeddings={cfg.max_position_embeddings}")
+            t = torch.arange(T)
+            blk = torch.full((Pb, T), cfg.pad_token_id, dtype=torch.long)
+            w = min(T, Tin)
+            blk[:, :w] = ids_c[s][:, :w]
+            blk = torch.where(t[None, :] < ln[:, None], blk, torch.full_like(blk, cfg.pad_token_id))
+            lab = torch.full((Pb, T), -100, dtype=torch.long)
+            lab[:, :w] = labels_all[s][:, :w]
+            ci, ti = (lab >= 0).nonzero(as_tuple=True)           # caption-major, positions ascending
+            n = ci.numel()
+            if n == 0:
+                continue
+            h32, h16 = bert.embed(blk.to(torch.int32).to(dev).view(-1), T, 0)
+            cdt = h16.dtype
+            if fused is None:                # the stack a DecoderSession runs (never a function of the batch)
+                fused = (os.environ.get("VIDIL_DECODE_FUSE_LN", "1") != "0" and not bert.parity and bert._text_fold_ok(cdt)
+                         and cfg.add_cross_attention)
+            NPs = (T + 15) // 16 * 16
+            # the block attends to itself through one scratch K / V^T pair shared by all layers (DecoderSession.prefill)
+            sk = torch.empty((1, Pb, H, T, 64), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
+            sv = torch.empty((1, Pb, H, 64, NPs), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
+            bert.run_layers(h32, h16, rows=Pb, T=T, self_k=sk, self_vt=sv, t_off=0, Tk_cap=T, NPs=NPs, causal=True, kv_len=None,
+                            cross=cross,
+                            cross_index=None if img_local is None else img_local.to(torch.int32).to(dev).contiguous(),
+                            cross_groups=None if g_local is None else g_local.to(torch.int32).to(dev).contiguous(),
+                            cross_max_group=mg, fused=fused)
+            d_rows = (ci * T + ti).to(dev)
+            d_labels = lab[ci, ti].to(torch.int32).to(dev)
+            for r0 in range(0, n, block_rows):
+                k = min(block_rows, n - r0)
+                need = (k + HEAD_GEMM_ROWS - 1) // HEAD_GEMM_ROWS * HEAD_GEMM_ROWS
+                if buf is None or buf.shape[0] < need:
+                    buf = None               # (release before growing)
+                    buf = torch.empty((need, V), dtype=torch.float32, device=dev)
+                lg = self.lm_logits_rows(h16, d_rows[r0:r0 + k], out=buf, h32=h32)
+                K.token_logprobs(lg, d_labels[r0:r0 + k], out_scores=scores[done + r0:done + r0 + k],
+                                 out_index=amax[done + r0:done + r0 + k])
+            done += n
+            caps.append(s[ci])
+            poss.append(ti + 1)
+        caption = torch.cat(caps) if caps else torch.zeros((0,), dtype=torch.long)
+        position = torch.cat(poss) if poss else torch.zeros((0,), dtype=torch.long)
+        lp, lpm = scores[:, 0], scores[:, 1]
+        # (a handful of floats per caption from here on: the 30,524-wide rows never reach a torch op)
+        token_loss = -lp if eps_ls == 0.0 else -((1.0 - eps_ls) * lp + eps_ls * lpm)
+        caption_d, position_d = caption.to(dev), position.to(dev)
+        table = torch.zeros((P, max(1, Tin)), dtype=torch.float64, device=dev)
+        table[caption_d, position_d] = token_loss.double()
+        count = torch.bincount(caption, minlength=P).to(torch.int32).to(dev)
+        return CaptionScores(loss_sum=table.sum(1).float(), count=count, lp_label=lp, lp_mean=lpm, argmax=amax,
+                             token_loss=token_loss, caption=caption_d, position=position_d)
+
     def forward(self, *a, **k):
-        raise NotImplementedError("use vidil_amd.blip.BLIP_Decoder.generate on the hot path")
+        raise NotImplementedError("BertLMHeadModel.forward (the HF signature) is not built: captions are generated by "
+                                  "vidil_amd.blip.BLIP_Decoder.generate and GIVEN captions are scored teacher-forced by "
+                                  "BertLMHeadModel.score / BLIP_Decoder.caption_nll (BLIP_Decoder.forward returns the loss)")
