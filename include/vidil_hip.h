@@ -404,6 +404,20 @@ int vidil_logsoftmax_topk(const float* logits, const float* beam_scores,
 /* 1.0).  A label >= V is an argument error, but labels live in device memory and   */
 /* the host cannot see them: the kernel treats such a row as ignored.  -inf logits  */
 /* are allowed (they carry probability 0; lp[label] stays finite, the mean is -inf).*/
+/* beams_in_logits == 0 selects this form.                                         */
+/*                                                                                 */
+/* nb == 0 and beams_in_logits = A > 0: the CANDIDATE form — the many-labels       */
+/* sibling (reference: models/blip_vqa.py:134-135, the probability of the first    */
+/* token of every answer of a list).  seqs holds A token ids SHARED by all rows    */
+/* (contiguous; ld_seqs is not read), and per row r of logits f32 [B, V]:          */
+/*   out_scores[r*A + a] = log_softmax(logits[r])[seqs[a]]     (a = 0 .. A-1)      */
+/*   out_index[r]        = argmax_j logits[r][j]   (lowest index on ties)          */
+/* out_scores f32 [B, A], out_index i32 [B].  The row is read ONCE for the (max,   */
+/* sum) pair, exactly as in the teacher-forced form (with A = 1 and seqs[0] = the  */
+/* label of every row, out_scores[r] is that form's out_scores[2r] bit for bit);   */
+/* the candidates are then gathered from the row.  A candidate < 0 or >= V, and a  */
+/* candidate whose logit is -inf, score -inf; no inf - inf is ever formed.         */
+/* beam_scores, ban_token, cur_len, ld_seqs and penalty are not read.              */
 int vidil_logsoftmax_topk_penalty(const float* logits, const float* beam_scores,
                                   int32_t B, int32_t nb, int32_t beams_in_logits,
                                   int32_t V, int32_t ban_token, const int32_t* seqs,

@@ -175,7 +175,8 @@ class DecoderSession:
         self.arena.init_prompt(P, self.nb if shared else 1)
         self.bert.run_layers(h32, h16, rows=rows, T=P, self_k=sk, self_vt=sv, t_off=0, Tk_cap=P, NPs=NPp, causal=True,
                              kv_len=None, cross=self.cross, cross_group=1 if shared else self.nb, ws=self.ws_prefill,
-                             arena=self.arena, arena_slot_stride=self.nb if shared else 1, fused=self.fused_ln)
+                             arena=self.arena, arena_slot_stride=self.nb if shared else 1, fused=self.fused_ln,
+                             arena_prompt=(P == 1 and shared))   # (a shared one-token prompt is still a prompt block: slot b*nb)
         return self.dec.lm_logits(h16, rows, P, h32=h32)
 
     def step(self, next_tok_i32, beam_idx_i32, past_len):

@@ -258,6 +258,13 @@ __device__ __forceinline__ void tf_four(TfState& s, const f32x4 x, int i) {
   }
 }
 
+// CANDS (vidil_logsoftmax_topk_penalty with num_beams == 0 and beams_in_logits = A > 0): the many-labels sibling — `labels`
+// holds A candidate token ids SHARED by all rows (ld_labels = A) and out_s is [rows, A]: out_s[r][a] = log_softmax(row r)[labels[a]]
+// (reference: models/blip_vqa.py:134-135, the first-token probabilities of an answer list).  Same first pass; every thread then
+// combines the four waves' states itself (same order as thread 0, so the same bits) and the workgroup strides over the candidates:
+// a gather from the 122 KB row it has just read, a coalesced store.  Candidates outside [0, V) and -inf logits score -inf
+// (never inf - inf).
+template <bool CANDS>
 __global__ __launch_bounds__(256) void tf_logprob_kernel(const float* __restrict__ logits, int V,
                                                          const int32_t* __restrict__ labels, int ld_labels,
                                                          float* __restrict__ out_s, int* __restrict__ out_i) {
@@ -289,7 +296,7 @@ __global__ __launch_bounds__(256) void tf_logprob_kernel(const float* __restrict
     red_m[tid >> 6] = wm; red_s[tid >> 6] = ws; red_t[tid >> 6] = wt; red_b[tid >> 6] = c;
   }
   __syncthreads();
-  if (tid != 0) return;
+  if (!CANDS && tid != 0) return;
   const float M = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
   float sum = 0.f, tot = 0.f;
   Cand g = red_b[0];
@@ -299,7 +306,22 @@ __global__ __launch_bounds__(256) void tf_logprob_kernel(const float* __restrict
     tot += red_t[w];
     if (w > 0 && better(red_b[w].s, red_b[w].i, g.s, g.i)) g = red_b[w];
   }
-  out_i[r] = g.i == 0x7fffffff ? 0 : g.i;          // (a row of -inf only has no maximum: index 0)
+  if (tid == 0) out_i[r] = g.i == 0x7fffffff ? 0 : g.i;          // (a row of -inf only has no maximum: index 0)
+  if (CANDS) {
+    const int A = ld_labels;
+    const float lse_c = logf(sum);
+    float* o = out_s + r * (size_t)A;
+    for (int a = tid; a < A; a += 256) {
+      const int c = labels[a];
+      float lp_c = -INFINITY;
+      if (c >= 0 && c < V) {
+        const float x = row[c];
+        if (x > -INFINITY) lp_c = (x - M) - lse_c;
+      }
+      o[a] = lp_c;
+    }
+    return;
+  }
   const int label = labels[r * (size_t)ld_labels];
   float lp = 0.f, lp_mean = 0.f;
   if (label >= 0 && label < V) {                   // (label < 0: ignored; label >= V cannot be refused by the host: ignored too)
@@ -450,14 +472,28 @@ extern "C" int vidil_logsoftmax_topk_penalty(const float* logits, const float* b
                                              int32_t beams_in_logits, int32_t V, int32_t ban_token, const int32_t* seqs,
                                              int32_t cur_len, int32_t ld_seqs, float penalty, float* out_scores,
                                              int32_t* out_index, void* stream) {
+  if (nb == 0 && beams_in_logits != 0) {
+    // candidate form: seqs holds beams_in_logits = A token ids shared by all rows, out_scores is [B, A]; beam_scores, ban_token,
+    // cur_len, ld_seqs and penalty are not read
+    const char* who = "logsoftmax_topk_penalty (num_beams=0, candidates)";
+    VIDIL_REQUIRE(beams_in_logits > 0, "%s: beams_in_logits=%d must be the number of candidates (> 0; 0: teacher-forced form)", who,
+                  beams_in_logits);
+    VIDIL_REQUIRE(seqs != nullptr, "%s: null candidate ids (seqs)", who);
+    VIDIL_REQUIRE(logits && out_scores && out_index, "%s: null pointer", who);
+    VIDIL_REQUIRE(B > 0 && V > 0, "%s: bad shape rows=%d V=%d", who, B, V);
+    hipLaunchKernelGGL(tf_logprob_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, V, seqs, beams_in_logits,
+                       out_scores, out_index);
+    VIDIL_CHECK_LAUNCH("logsoftmax_topk_penalty (candidates)");
+    return VIDIL_OK;
+  }
   if (nb == 0) {
-    // teacher-forced form: seqs holds one label per row (row stride ld_seqs); beam_scores, beams_in_logits, ban_token,
-    // cur_len and penalty are not read
+    // teacher-forced form: seqs holds one label per row (row stride ld_seqs); beam_scores, ban_token, cur_len and penalty are
+    // not read (beams_in_logits == 0)
     VIDIL_REQUIRE(seqs != nullptr, "logsoftmax_topk_penalty (num_beams=0, teacher-forced): null labels (seqs)");
     VIDIL_REQUIRE(logits && out_scores && out_index, "logsoftmax_topk_penalty (num_beams=0, teacher-forced): null pointer");
     VIDIL_REQUIRE(B > 0 && V > 0, "logsoftmax_topk_penalty (num_beams=0, teacher-forced): bad shape rows=%d V=%d", B, V);
     VIDIL_REQUIRE(ld_seqs >= 1, "logsoftmax_topk_penalty (num_beams=0, teacher-forced): ld_seqs=%d must be >= 1", ld_seqs);
-    hipLaunchKernelGGL(tf_logprob_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, V, seqs, ld_seqs, out_scores,
+    hipLaunchKernelGGL(tf_logprob_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, V, seqs, ld_seqs, out_scores,
                        out_index);
     VIDIL_CHECK_LAUNCH("logsoftmax_topk_penalty (teacher-forced)");
     return VIDIL_OK;

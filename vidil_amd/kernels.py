@@ -488,6 +488,31 @@ def token_logprobs(logits, labels, out_scores=None, out_index=None):
     return out_scores[:, 0], out_scores[:, 1], out_index
 
 
+def candidate_logprobs(logits, cand, out=None, out_index=None):
+    """Log-probabilities of a candidate list shared by all rows (vidil_logsoftmax_topk_penalty with num_beams == 0 and
+    beams_in_logits = A; reference: models/blip_vqa.py:134-135, the first tokens of an answer list): logits f32 [R, V], cand
+    i32 [A] -> out f32 [R, A] with out[r, a] = log_softmax(logits[r])[cand[a]]; a candidate outside [0, V) scores -inf.
+    ``out_index`` i32 [R] receives every row's argmax (lowest index on ties).  One read of the logits."""
+    if logits.dim() != 2 or cand.dim() != 1 or cand.numel() == 0:
+        raise VidilHipError(f"candidate_logprobs: logits [R, V] and a non-empty cand [A] expected, got {tuple(logits.shape)} / {tuple(cand.shape)}")
+    R, V = logits.shape
+    A = cand.numel()
+    dev = logits.device
+    if out is None:
+        out = torch.empty((R, A), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (R, A):
+        raise VidilHipError(f"candidate_logprobs: out must be f32 [{R}, {A}], got {tuple(out.shape)}")
+    if out_index is None:
+        out_index = torch.empty((R,), dtype=torch.int32, device=dev)
+    if R:
+        check(_lib.load().vidil_logsoftmax_topk_penalty(_ptr(logits, torch.float32, "candidate_logprobs.logits"), None, R, 0, A, V, -1,
+                                                        _ptr(cand, torch.int32, "candidate_logprobs.cand"), 0, 1, 1.0,
+                                                        _ptr(out, torch.float32, "candidate_logprobs.out"),
+                                                        _ptr(out_index, torch.int32, "candidate_logprobs.out_index"), _stream()),
+              "candidate_logprobs")
+    return out
+
+
 class BeamBuffers:
     """Device-resident beam-search state for ``B`` images x ``nb`` beams."""
 

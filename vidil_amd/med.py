@@ -293,7 +293,8 @@ class BertModel(PackedCache, nn.Module):
         return out
 
     # --------------------------------------------------------- cross K/V (once per image)
-    def project_cross_kv(self, enc16, B, Te, out: "CrossKV" = None, v_rowmajor=False, last_layer_vt=False, tiled=False):
+    def project_cross_kv(self, enc16, B, Te, out: "CrossKV" = None, v_rowmajor=False, last_layer_vt=False, tiled=False,
+                         kv_len=None):
         """enc16: f16 [B*Te, encoder_width] image tokens.  One fused K|V GEMM per layer.  ``out``: buffers of a
         previous call with the same (B, Te) to overwrite (keeps device addresses stable for captured graphs).
         ``v_rowmajor``: keep V as [L][B,H,Te,64] (NP = 0) — for consumers whose every cross-attention launch has more
@@ -301,10 +302,19 @@ class BertModel(PackedCache, nn.Module):
         ``last_layer_vt`` (with v_rowmajor): the last layer's V goes to a V^T buffer instead (``last_vt``) — its
         consumer is encode_cls, whose last layer has one query row per pair.
         ``tiled``: K and V in 32-key fragment tiles — for consumers whose every launch has at most 32 query rows per
-        image and which re-read the K/V from HBM many times (the decode steps of the captioner)."""
+        image and which re-read the K/V from HBM many times (the decode steps of the captioner).
+        ``kv_len`` (int [B], device): unit b holds kv_len[b] real encoder states followed by padding (the question states of
+        BLIP_VQA); the padding rows are cleared before the projection.  The attention kernels mask the SCORES of the keys past
+        ``cross_kv_len`` and still multiply those keys' values by the resulting zero probabilities, so a non-finite pad state
+        would reach the output as 0 x NaN; cleared rows project to the bias.  With it no pad state is read into a result."""
         p = self.packed()
         H = self.config.num_attention_heads
         cdt = enc16.dtype
+        if kv_len is not None:
+            if p["parity"]:
+                raise K.VidilHipError("project_cross_kv: kv_len (padded encoder units) is not built for the parity precision mode")
+            keep = torch.arange(Te, device=enc16.device)[None, :] < kv_len.to(enc16.device).view(B, 1)
+            enc16 = torch.where(keep.view(B * Te, 1), enc16, torch.zeros((), dtype=cdt, device=enc16.device)).contiguous()
         if p["parity"]:
             # parity precision mode: enc16 holds [hi | lo | hi] rows of the image tokens (the ViT's parity output)
             if enc16.shape[1] != 3 * self.config.encoder_width:
@@ -376,7 +386,7 @@ class BertModel(PackedCache, nn.Module):
     def run_layers(self, h32, h16, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len,
                    cross: CrossKV, cross_index=None, cross_group=1, cross_groups=None, cross_max_group=0, ws=None,
                    arena: "BeamArena" = None, arena_slot_stride=1, n_layers=None, self_done_first=False,
-                   stop_after_self=False, fused=None):
+                   stop_after_self=False, fused=None, cross_kv_len=None, arena_prompt=False):
         """Run every layer on the f32/f16 hidden pair (both [rows*T, C], updated in place).
 
         self_k / self_vt: [L][rows,H,Tk_cap,64] / [L][rows,H,64,NPs] — this call's keys are appended at
@@ -386,6 +396,12 @@ class BertModel(PackedCache, nn.Module):
         arena[position t_off][slot r] and attention follows the row's ancestry (self_k / self_vt unused);
         with T > 1 (prompt pass, t_off == 0) attention runs over the block as above and the block's K/V are
         ALSO written to the arena at slots r*arena_slot_stride.
+
+        arena_prompt: a ONE-token block at position 0 is a prompt block, not a decode step (a search that starts from the
+        start token alone, models/blip_vqa.py:97): it takes the T > 1 route, so its K/V land at slots r*arena_slot_stride.
+
+        cross_kv_len (i32 [rows], device; default None: every one of cross.Te keys): query batch r attends to the first
+        cross_kv_len[r] keys of its encoder unit only (a decoder over padded question states: models/blip_vqa.py:69-76,125-129).
         """
         p = self.packed()
         cfg = self.config
@@ -399,6 +415,10 @@ class BertModel(PackedCache, nn.Module):
                 raise K.VidilHipError("run_layers: the parity precision mode runs whole stacks (the caption decoder, "
                                       "BertModel.encode); encode_cls' split schedules are not built for it — BLIP_ITM.itm_pairs "
                                       "takes encode_cls_parity (or the encode() route) in that mode")
+            if cross_kv_len is not None:
+                raise K.VidilHipError("run_layers: cross_kv_len (masked cross-attention) is not built for the parity precision mode")
+            if arena_prompt:
+                raise K.VidilHipError("run_layers: a one-token prompt block (arena_prompt) is not built for the parity precision mode")
             return self._run_layers_parity(p, h32, h16, rows=rows, T=T, self_k=self_k, self_vt=self_vt, t_off=t_off,
                                            Tk_cap=Tk_cap, NPs=NPs, causal=causal, kv_len=kv_len, cross=cross,
                                            cross_index=cross_index, cross_group=cross_group, cross_groups=cross_groups,
@@ -417,7 +437,7 @@ class BertModel(PackedCache, nn.Module):
                                           NPs=NPs, causal=causal, kv_len=kv_len, cross=cross, cross_index=cross_index,
                                           cross_group=cross_group, cross_groups=cross_groups, cross_max_group=cross_max_group,
                                           n_layers=n_layers, self_done_first=self_done_first, arena=arena,
-                                          arena_slot_stride=arena_slot_stride)
+                                          arena_slot_stride=arena_slot_stride, cross_kv_len=cross_kv_len, arena_prompt=arena_prompt)
         if ws is None:
             ws = {}
         q = ws.get("q")
@@ -430,13 +450,14 @@ class BertModel(PackedCache, nn.Module):
         Nk = t_off + T
         if arena is not None and T > 1 and t_off != 0:
             raise K.VidilHipError("run_layers: a multi-token block can only be appended to a beam arena at position 0")
+        ckl = self._cross_len_arg(cross_kv_len, rows)
         # n_layers: only the first n (encode_cls runs the last itself).  self_done_first / stop_after_self split layer
         # 0 after its self-attention block (dense + residual + LayerNorm included): that block does not see the image,
         # so encode_cls runs it once per TEXT and the rest of the stack once per (image, text) pair.
         for i, d in enumerate(p["layers"][:n_layers]):
             if self_done_first and i == 0:
                 pass
-            elif arena is not None and T == 1:
+            elif arena is not None and T == 1 and not arena_prompt:
                 K.gemm(h16, d["qkv_w"], d["qkv_b"],
                        arena=dict(q=q, k=arena.k[i], v=arena.v[i], T=1, H=H, part0=0, t_off=t_off, Tcap=arena.Tcap,
                                   arena_rows=arena.rows, slot_stride=1, q_scale=0.125))
@@ -464,13 +485,24 @@ class BertModel(PackedCache, nn.Module):
                     r0, r1 = (0, rows) if (b0, b1) == (0, cross.B) else (b0 * cross_group, b1 * cross_group)
                     K.attention(q[r0:r1], cross.k[i][b0:b1], cross.vt[i][b0:b1], o[r0 * T:r1 * T], Bq=r1 - r0, H=H, Nq=T, Nk=cross.Te,
                                 Tq_cap=T, Tk_cap=cross.Tk_cap, NP=cross.NP, kv_group=cross_group, kv_index=cross_index,
-                                group_start=cross_groups, max_group=cross_max_group, kv_tiled=cross.tiled)
+                                group_start=cross_groups, max_group=cross_max_group, kv_tiled=cross.tiled, **ckl(r0, r1))
                 K.gemm(o, d["co_w"], d["co_b"], out=tmp, resid=h32)
                 K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=h16, out32=h32)
             K.gemm(h16, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
             K.gemm(inter, d["o_w"], d["o_b"], out=tmp, resid=h32)
             K.layernorm(tmp, d["o_g"], d["o_bt"], eps, out16=h16, out32=h32)
         return h32, h16
+
+    @staticmethod
+    def _cross_len_arg(cross_kv_len, rows):
+        """(r0, r1) -> the ``kv_len`` keyword of a cross-attention launch over query batches r0 .. r1-1: nothing when the call has
+        no cross_kv_len (the launch then is exactly what it was before the argument existed), else its slice of the table."""
+        if cross_kv_len is None:
+            return lambda r0, r1: {}
+        if cross_kv_len.dtype != torch.int32 or cross_kv_len.dim() != 1 or cross_kv_len.numel() != rows or not cross_kv_len.is_contiguous():
+            raise K.VidilHipError(f"run_layers: cross_kv_len must be a contiguous i32 [{rows}] tensor (one length per query batch), got "
+                                  f"{cross_kv_len.dtype} {tuple(cross_kv_len.shape)}")
+        return lambda r0, r1: dict(kv_len=cross_kv_len[r0:r1])
 
     def _cross_blocks(self, cross, cross_index, cross_groups):
         """Image ranges [b0, b1) of the cross-attention launches of one layer: the whole batch, or — uniform grouping (a beam
@@ -482,12 +514,14 @@ class BertModel(PackedCache, nn.Module):
         return [(b0, min(B, b0 + n)) for b0 in range(0, B, n)]
 
     def _run_layers_parity(self, p, h32, h3, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len, cross, cross_index,
-                           cross_group, cross_groups, cross_max_group, ws, arena, arena_slot_stride, n_layers=None):
+                           cross_group, cross_groups, cross_max_group, ws, arena, arena_slot_stride, n_layers=None, cross_kv_len=None):
         """run_layers in the parity precision mode: ``h3`` [rows*T, 3C] carries the hidden states as [hi | lo | hi]
         operand rows, every GEMM runs against [W_hi | W_hi | W_lo] with K tripled, LayerNorm / attention write split rows
         directly and the GELU output goes through f32 + vidil_split3_f32.  Same launch sequence otherwise.
         n_layers: only the first n layers (encode_cls_parity runs the last itself); ws["planes_h"] then tells it how many
         planes of ``h3`` the last of them wrote."""
+        if cross_kv_len is not None:
+            raise K.VidilHipError("_run_layers_parity: cross_kv_len (masked cross-attention) is not built for the parity precision mode")
         cfg = self.config
         H, C = cfg.num_attention_heads, cfg.hidden_size
         eps = cfg.layer_norm_eps
@@ -610,7 +644,8 @@ class BertModel(PackedCache, nn.Module):
 
     def _run_layers_fused(self, h32, h16, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len, cross, cross_index=None,
                           cross_group=1, cross_groups=None, cross_max_group=0, n_layers=None, self_done_first=False,
-                          stop_after_self=False, state_in=None, arena: "BeamArena" = None, arena_slot_stride=1):
+                          stop_after_self=False, state_in=None, arena: "BeamArena" = None, arena_slot_stride=1, cross_kv_len=None,
+                          arena_prompt=False):
         """run_layers for encoder batches with cross-attention, WITHOUT LayerNorm launches between the GEMMs
         (models/med.py:236-239,306-317 are post-LN: h = LN(x + dense(.)) is the next dense's input AND the next residual).
         The stream is kept as the RAW sums u (f32 in h32's storage, a 16-bit copy in h16's) plus per-row (sum, sum of
@@ -674,11 +709,12 @@ class BertModel(PackedCache, nn.Module):
             wf, bf, cs = fw[i]["qkv"]
             return K.gemm(h16, wf[C:], bf[C:], ln=(cs[C:], eps, stats[cur]), **kw)
 
+        ckl = self._cross_len_arg(cross_kv_len, rows)
         layers = p["layers"][:n_layers]
         for i, d in enumerate(layers):
             if self_done_first and i == 0:
                 pass
-            elif arena is not None and T == 1:
+            elif arena is not None and T == 1 and not arena_prompt:
                 consumer("qkv", i, d["qkv_w"], d["qkv_b"],
                          arena=dict(q=q, k=arena.k[i], v=arena.v[i], T=1, H=H, part0=0, t_off=t_off, Tcap=arena.Tcap,
                                     arena_rows=arena.rows, slot_stride=1, q_scale=0.125))
@@ -700,7 +736,7 @@ class BertModel(PackedCache, nn.Module):
                 r0, r1 = (0, rows) if (b0, b1) == (0, cross.B) else (b0 * cross_group, b1 * cross_group)
                 K.attention(q[r0:r1], cross.k[i][b0:b1], cross.vt[i][b0:b1], o[r0 * T:r1 * T], Bq=r1 - r0, H=H, Nq=T, Nk=cross.Te,
                             Tq_cap=T, Tk_cap=cross.Tk_cap, NP=cross.NP, kv_group=cross_group, kv_index=cross_index,
-                            group_start=cross_groups, max_group=cross_max_group, kv_tiled=cross.tiled)
+                            group_start=cross_groups, max_group=cross_max_group, kv_tiled=cross.tiled, **ckl(r0, r1))
             residual_gemm(o, d["co_w"], d["co_b"], d["co_g"], d["co_bt"])
             consumer("fc1", i, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
             residual_gemm(inter, d["o_w"], d["o_b"], d["o_g"], d["o_bt"])
@@ -1020,9 +1056,63 @@ class BertLMHeadModel(PackedCache, nn.Module):
             K.gemm(t16[r0:r0 + G], p["dec_w"], p["dec_b"], out=out[r0:r0 + G])
         return out[:n]
 
+    def _causal_block_pass(self, ids_i32, rows, T, cross, **cross_kw):
+        """The ONE stack pass of ``score`` and ``start_logits``: ids i32 [rows*T] (device) -> (h32, h16) [rows*T, C] after a
+        causal pass in which every block of T tokens attends to itself through one scratch K / V^T pair shared by all layers
+        (as DecoderSession.prefill does for a prompt) and to ``cross`` (cross_kw: cross_index / cross_groups / cross_max_group /
+        cross_kv_len).  The stack is the one a DecoderSession runs (LN-folded or parity) — never a function of the batch."""
+        bert, cfg = self.bert, self.config
+        H, L = cfg.num_attention_heads, cfg.num_hidden_layers
+        dev = ids_i32.device
+        h32, h16 = bert.embed(ids_i32, T, 0)
+        cdt = h16.dtype
+        fused = (os.environ.get("VIDIL_DECODE_FUSE_LN", "1") != "0" and not bert.parity and bert._text_fold_ok(cdt)
+                 and cfg.add_cross_attention)
+        NPs = (T + 15) // 16 * 16
+        sk = torch.empty((1, rows, H, T, 64), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
+        sv = torch.empty((1, rows, H, 64, NPs), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
+        bert.run_layers(h32, h16, rows=rows, T=T, self_k=sk, self_vt=sv, t_off=0, Tk_cap=T, NPs=NPs, causal=True, kv_len=None,
+                        cross=cross, fused=fused, **cross_kw)
+        return h32, h16
+
+    @torch.no_grad()
+    def start_logits(self, enc16, B, start_id, *, cross_kv_len=None):
+        """Logits of the first generated token: one decoder pass of the start token alone per encoder unit
+        (models/blip_vqa.py:123-130).  enc16: 16-bit [B*Te, width] encoder states of B units; cross_kv_len int [B]: real states
+        per unit (the rest is padding, masked).  Returns f32 [B, V].
+
+        Schedule: the pass ``score`` runs — the start token heads a causal block of SCORE_MIN_TOKENS tokens whose other
+        positions are padding it never sees —, so both stages of an answer ranking go through the same kernels whatever the
+        batch holds, and position 0 goes through the LM head in HEAD_GEMM_ROWS-row launches (``lm_logits_rows``)."""
+        require_cuda(enc16, "BertLMHeadModel.start_logits")
+        bert, cfg = self.bert, self.config
+        dev = enc16.device
+        T = SCORE_MIN_TOKENS
+        if B <= 0 or enc16.shape[0] % B:
+            raise ValueError(f"start_logits: {enc16.shape[0]} encoder rows do not divide into B={B} units")
+        Te = enc16.shape[0] // B
+        ckl = None
+        if cross_kv_len is not None:
+            ckl = torch.as_tensor(cross_kv_len).cpu().long().view(-1)
+            if ckl.numel() != B or int(ckl.min()) < 1 or int(ckl.max()) > Te:
+                raise ValueError(f"start_logits: cross_kv_len must hold {B} lengths in [1, {Te}]")
+            ckl = ckl.to(torch.int32).to(dev)
+        out = torch.empty((B, cfg.vocab_size), dtype=torch.float32, device=dev)
+        for b0 in range(0, B, bert.MAX_IMAGES_PER_LAUNCH):
+            b1 = min(B, b0 + bert.MAX_IMAGES_PER_LAUNCH)
+            n = b1 - b0
+            kw_p, kw_r = ({}, {}) if ckl is None else (dict(kv_len=ckl[b0:b1]), dict(cross_kv_len=ckl[b0:b1].contiguous()))
+            cross = bert.project_cross_kv(enc16[b0 * Te:b1 * Te], n, Te, v_rowmajor=True, **kw_p)
+            blk = torch.full((n, T), cfg.pad_token_id, dtype=torch.int32, device=dev)
+            blk[:, 0] = int(start_id)
+            h32, h16 = self._causal_block_pass(blk.view(-1), n, T, cross, **kw_r)
+            rows = torch.arange(n, device=dev) * T
+            out[b0:b1].copy_(self.lm_logits_rows(h16, rows, h32=h32))
+        return out
+
     @torch.no_grad()
     def score(self, enc16, B, ids, lens, *, image_index=None, group_start=None, max_group=0, label_smoothing=0.1,
-              prompt_length):
+              prompt_length, cross_kv_len=None):
         """Teacher-forced scores of GIVEN captions (models/med.py:886-917 with labels; models/blip.py:104-125 builds them).
 
         enc16: image tokens of B images, 16-bit [B*Te, width] ([hi | lo | hi] rows in the parity mode).  ids int [P, T]
@@ -1031,6 +1121,9 @@ class BertLMHeadModel(PackedCache, nn.Module):
         (at most max_group each; 0: taken from the table).  The logits at position t are scored against token t + 1 for
         prompt_length - 1 <= t <= lens - 2 (``teacher_forced_targets``); a caption's loss is the sum over its targets of
         (1 - eps) * (-lp[label]) + eps * (-mean_j lp[j]), eps = label_smoothing.  Returns a ``CaptionScores``.
+        ``cross_kv_len`` (int [B]): encoder unit b holds cross_kv_len[b] real states followed by padding up to Te (question
+        states, models/blip_vqa.py:69-76,153-159); every caption attends to the real states of its unit only — the length is
+        expanded per caption through image_index / group_start.  Not built for the parity mode.
 
         Schedule: one causal pass over blocks of T = max(lens) tokens (at least SCORE_MIN_TOKENS) per caption — no KV arena,
         the right padding is hidden by the causal mask —, the stack a DecoderSession runs (LN-folded / parity); cross K/V
@@ -1053,6 +1146,11 @@ class BertLMHeadModel(PackedCache, nn.Module):
         if B <= 0 or enc16.shape[0] % B:
             raise ValueError(f"score: {enc16.shape[0]} image-token rows do not divide into B={B} images")
         Te = enc16.shape[0] // B
+        ckl_c = None
+        if cross_kv_len is not None:
+            ckl_c = torch.as_tensor(cross_kv_len).cpu().long().view(-1)
+            if ckl_c.numel() != B or int(ckl_c.min()) < 1 or int(ckl_c.max()) > Te:
+                raise ValueError(f"score: cross_kv_len must hold {B} lengths in [1, {Te}]")
         n_img = bert.MAX_IMAGES_PER_LAUNCH
         # ---- passes: (first image, last image + 1, caption indices, their image within the block | group table, max group)
         passes = []
@@ -1096,10 +1194,10 @@ class BertLMHeadModel(PackedCache, nn.Module):
         buf = None
         cross, cross_of = None, None
         done = 0
-        fused = None
         for b0, b1, s, img_local, g_local, mg in passes:
             if cross_of != (b0, b1):         # (more than 32 query rows per image in every launch: row-major values)
-                cross = bert.project_cross_kv(enc16[b0 * Te:b1 * Te], b1 - b0, Te, v_rowmajor=True)
+                cross = bert.project_cross_kv(enc16[b0 * Te:b1 * Te], b1 - b0, Te, v_rowmajor=True,
+                                              **({} if ckl_c is None else dict(kv_len=ckl_c[b0:b1].to(dev))))
                 cross_of = (b0, b1)
             Pb = s.numel()
             ln = lens_c[s]
@@ -1117,20 +1215,13 @@ class BertLMHeadModel(PackedCache, nn.Module):
             n = ci.numel()
             if n == 0:
                 continue
-            h32, h16 = bert.embed(blk.to(torch.int32).to(dev).view(-1), T, 0)
-            cdt = h16.dtype
-            if fused is None:                # the stack a DecoderSession runs (never a function of the batch)
-                fused = (os.environ.get("VIDIL_DECODE_FUSE_LN", "1") != "0" and not bert.parity and bert._text_fold_ok(cdt)
-                         and cfg.add_cross_attention)
-            NPs = (T + 15) // 16 * 16
-            # the block attends to itself through one scratch K / V^T pair shared by all layers (DecoderSession.prefill)
-            sk = torch.empty((1, Pb, H, T, 64), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
-            sv = torch.empty((1, Pb, H, 64, NPs), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
-            bert.run_layers(h32, h16, rows=Pb, T=T, self_k=sk, self_vt=sv, t_off=0, Tk_cap=T, NPs=NPs, causal=True, kv_len=None,
-                            cross=cross,
-                            cross_index=None if img_local is None else img_local.to(torch.int32).to(dev).contiguous(),
-                            cross_groups=None if g_local is None else g_local.to(torch.int32).to(dev).contiguous(),
-                            cross_max_group=mg, fused=fused)
+            cross_kw = dict(cross_index=None if img_local is None else img_local.to(torch.int32).to(dev).contiguous(),
+                            cross_groups=None if g_local is None else g_local.to(torch.int32).to(dev).contiguous(), cross_max_group=mg)
+            if ckl_c is not None:            # every caption attends to the real states of its unit only
+                unit = ckl_c[b0:b1]
+                per = unit[img_local] if img_local is not None else unit.repeat_interleave(g_local[1:] - g_local[:-1])
+                cross_kw["cross_kv_len"] = per.to(torch.int32).to(dev).contiguous()
+            h32, h16 = self._causal_block_pass(blk.to(torch.int32).to(dev).view(-1), Pb, T, cross, **cross_kw)
             d_rows = (ci * T + ti).to(dev)
             d_labels = lab[ci, ti].to(torch.int32).to(dev)
             for r0 in range(0, n, block_rows):

@@ -54,6 +54,8 @@ def set_compute_dtype(dtype, *modules):
         _default[0] = dtype
         return dtype
     for m in modules:
+        if dtype == FP8 and getattr(m, "plain_only", None):
+            raise ValueError(f"{type(m).__name__}: fp8 is refused — {m.plain_only}")
         for sub in m.modules():
             sub.__dict__["_compute_dtype"] = dtype
     return dtype
@@ -88,6 +90,8 @@ def set_parity_mode(on, *modules):
         _parity_default[0] = on
         return on
     for m in modules:
+        if on and getattr(m, "plain_only", None):      # (a model class states why it runs on plain 16-bit operands only)
+            raise ValueError(f"{type(m).__name__}: the parity precision mode is refused — {m.plain_only}")
         for sub in m.modules():
             sub.__dict__["_parity"] = on
     return on
