@@ -19,7 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .packing import FP8, PackedCache, fold_layernorm, parity_attention_arith, parity_attention_f32, require_cuda, v32, w3, w3_patch, w8, w16, w16_patch
+from .packing import PackedCache, parity_attention_arith, parity_attention_f32, require_cuda, v32, w3, w3_patch, w16, w16_patch
+from .tower import pack_layer, run_layers
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -119,148 +120,16 @@ class _TextModel(nn.Module):
         self.final_layer_norm = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
 
 
-def _pack_layers(encoder, c, fuse=False, fp8=False, parity=False):
-    """fuse: LayerNorm folded into the QKV / fc1 GEMMs (layer_norm2 everywhere, layer_norm1 from layer 1 on: layer
-    0's input is written by a stand-alone LayerNorm / embedding kernel, not by a residual GEMM).
-    parity: [W_hi | W_hi | W_lo] operands of the error-compensated GEMMs (packing.set_parity_mode)."""
+def _pack_layers(encoder, c, form="plain"):
+    """tower.pack_layer of every layer of an HF-named encoder (form: plain | fold | fp8 | parity)."""
+    wb = lambda m: (m.weight, m.bias)
     out = []
     for i, l in enumerate(encoder.layers):
         a = l.self_attn
-        extra = {}
-        if parity:
-            extra["qkv_w3"] = w3(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, dtype=c)
-            extra["o_w3"] = w3(a.out_proj.weight, dtype=c)
-            extra["fc1_w3"] = w3(l.mlp.fc1.weight, dtype=c)
-            extra["fc2_w3"] = w3(l.mlp.fc2.weight, dtype=c)
-        elif fp8:     # fp8 tower mode (see vit.VisionTransformer._run_blocks_fp8)
-            extra["qkv_w8"], extra["qkv_s"] = w8(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight)
-            extra["o_w8"], extra["o_s"] = w8(a.out_proj.weight)
-            extra["fc1_w8"], extra["fc1_s"] = w8(l.mlp.fc1.weight)
-            extra["fc2_w8"], extra["fc2_s"] = w8(l.mlp.fc2.weight)
-        elif fuse:
-            extra["fc1_f"] = fold_layernorm(l.mlp.fc1.weight, l.mlp.fc1.bias, l.layer_norm2.weight, l.layer_norm2.bias, c)
-            if i > 0:
-                qkv_w = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], dim=0)
-                qkv_b = torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], dim=0)
-                extra["qkv_f"] = fold_layernorm(qkv_w, qkv_b, l.layer_norm1.weight, l.layer_norm1.bias, c)
-        out.append(dict(extra, 
-            n1g=v32(l.layer_norm1.weight), n1b=v32(l.layer_norm1.bias),
-            qkv_w=w16(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, dtype=c),
-            qkv_b=v32(a.q_proj.bias, a.k_proj.bias, a.v_proj.bias),
-            o_w=w16(a.out_proj.weight, dtype=c), o_b=v32(a.out_proj.bias),
-            n2g=v32(l.layer_norm2.weight), n2b=v32(l.layer_norm2.bias),
-            fc1_w=w16(l.mlp.fc1.weight, dtype=c), fc1_b=v32(l.mlp.fc1.bias),
-            fc2_w=w16(l.mlp.fc2.weight, dtype=c), fc2_b=v32(l.mlp.fc2.bias)))
+        out.append(pack_layer(wb(l.layer_norm1), (a.q_proj.weight, a.k_proj.weight, a.v_proj.weight),
+                              (a.q_proj.bias, a.k_proj.bias, a.v_proj.bias), wb(a.out_proj), wb(l.layer_norm2), wb(l.mlp.fc1),
+                              wb(l.mlp.fc2), dtype=c, form=form, fold_qkv=i > 0))
     return out
-
-
-def _run_layers(layers, x, B, T, H, eps, *, causal=False, kv_len=None, f32_attn=True, arith=0, cls_last=False):
-    """Pre-LN CLIP encoder layers on the f32 residual stream x [B*T, D] (in place).
-    cls_last (the vision tower in the parity precision mode with the f32-row attention kinds, round 6): the caller reads token 0
-    of every image only (pooled output = post_layernorm(CLS), HF CLIPVisionTransformer), so the LAST layer computes K | V for all
-    rows and everything else — the query, the attention output, out-proj, LayerNorm 2, fc1, fc2 — for the B class-token rows alone
-    (10/12 of that layer's GEMM rows are not computed: ~7 % of the tower); returns the f32 CLS rows [B, D] instead of x.
-    Per class-token row the arithmetic is the full layer's (its attention in plain f32 arithmetic instead of the split form)."""
-    dev = x.device
-    M, D = x.shape
-    cdt = layers[0]["qkv_w"].dtype
-    # more than 32 rows -> LDS-staged attention, which takes V row-major (NP = 0: plain 16-B stores from the QKV GEMM);
-    # short text batches go through the direct kernels, which read V^T fragments straight from memory
-    NP = 0 if T > 32 else (T + 15) // 16 * 16
-    xn = torch.empty((M, D), dtype=cdt, device=dev)
-    q = torch.empty((B, H, T, 64), dtype=cdt, device=dev)
-    k = torch.empty((B, H, T, 64), dtype=cdt, device=dev)
-    vt = torch.empty((B, H, T, 64) if NP == 0 else (B, H, 64, NP), dtype=cdt, device=dev)
-    o = torch.empty((M, D), dtype=cdt, device=dev)
-    hid = torch.empty((M, layers[0]["fc1_w"].shape[0]), dtype=cdt, device=dev)
-    heads = dict(q=q, k=k, vt=vt, T=T, H=H, part0=0, t_off=0, Tq_cap=T, Tk_cap=T, NP=NP, q_scale=0.125)
-    n = len(layers)
-    if "qkv_w3" in layers[0]:
-        # Parity precision mode (round 4; as vit.VisionTransformer._run_blocks_parity): every GEMM on error-compensated
-        # operands — LayerNorm and attention write [hi | lo | hi] rows (VIDIL_DT_SPLIT3), the quick-GELU output goes through
-        # the GEMM's own split3 epilogue, weights are [W_hi | W_hi | W_lo], K tripled.  Attention: vidil_attention_f32 on the f32
-        # Q | K | V rows (split-operand MFMA by default, or f32 arithmetic), or — kind "16" — the 16-bit kernels.
-        Dh = layers[0]["fc1_w"].shape[0]
-        a3 = torch.empty((M, 3 * D), dtype=cdt, device=dev)
-        o3 = torch.empty((M, 3 * D), dtype=cdt, device=dev)
-        hid3 = torch.empty((M, 3 * Dh), dtype=cdt, device=dev)
-        # (planes hi | lo only where EVERY consumer of the rows takes the K-loop form — asked per call, vit.py has the reasoning;
-        #  the consumers state a_planes so that a launch that would read an unwritten plane fails instead)
-        qkv32 = torch.empty((M, 3 * D), dtype=torch.float32, device=dev) if f32_attn else None
-        planes, l0 = 3, layers[0]
-        qkv_kw = dict(out=qkv32) if f32_attn else dict(heads=heads)
-        if (K.split_k_serves(a3, l0["qkv_w3"], l0["qkv_b"], **qkv_kw) and K.split_k_serves(o3, l0["o_w3"], l0["o_b"], out=x, resid=x)
-                and K.split_k_serves(a3, l0["fc1_w3"], l0["fc1_b"], split3_out=hid3, act=K.ACT_QUICK_GELU)
-                and K.split_k_serves(hid3, l0["fc2_w3"], l0["fc2_b"], out=x, resid=x)):
-            planes = 2
-        K.poison_third_plane(planes, a3, o3, hid3)
-        cls_last = cls_last and f32_attn and not causal and kv_len is None and T > 1
-        for li, l in enumerate(layers):
-            K.layernorm(x, l["n1g"], l["n1b"], eps, out16=a3, split3=True, planes=planes)
-            if cls_last and li == n - 1:
-                # ---- last layer, class-token rows only (K | V still for every token)
-                kv32 = qkv32.view(-1)[:M * 2 * D].view(M, 2 * D)               # (the layers' scratch, re-shaped: [M, 2D] keys | values)
-                K.gemm(a3, l["qkv_w3"][D:], l["qkv_b"][D:], out=kv32, split_k=True, a_planes=planes)
-                a3c = a3.view(B, T, 3 * D)[:, 0].contiguous()                  # [B, 3D] operand rows of the class tokens
-                if planes == 2:
-                    a3c[:, 2 * D:] = a3c[:, :D]                                # (three valid planes: the small launches below may be plain)
-                q32c = K.gemm(a3c, l["qkv_w3"][:D], l["qkv_b"][:D], out_dtype=torch.float32, split_k=True)
-                o3c = torch.empty((B, 3 * D), dtype=cdt, device=dev)
-                K.attention_f32(q32c, kv32[:, :D], kv32[:, D:], o3c, Bq=B, H=H, Nq=1, Nk=T, kv_rows=T, arith=0, planes=3)
-                xc = x.view(B, T, D)[:, 0].contiguous()                        # [B, D] f32 residual rows of the class tokens
-                K.gemm(o3c, l["o_w3"], l["o_b"], out=xc, resid=xc, split_k=True)
-                K.layernorm(xc, l["n2g"], l["n2b"], eps, out16=a3c, split3=True, planes=3)
-                h3c = K.gemm(a3c, l["fc1_w3"], l["fc1_b"], split3_out=torch.empty((B, 3 * Dh), dtype=cdt, device=dev), act=K.ACT_QUICK_GELU,
-                             split_k=True, split3_planes=3)
-                K.gemm(h3c, l["fc2_w3"], l["fc2_b"], out=xc, resid=xc, split_k=True)
-                return xc
-            if f32_attn:    # (Q | K | V stay f32 and row-major: vidil_attention_f32 reads them in place)
-                K.gemm(a3, l["qkv_w3"], l["qkv_b"], out=qkv32, split_k=True, a_planes=planes)
-                K.attention_f32(qkv32[:, :D], qkv32[:, D:2 * D], qkv32[:, 2 * D:], o3, Bq=B, H=H, Nq=T, Nk=T, causal=causal, kv_len=kv_len,
-                                arith=arith, planes=planes)
-            else:
-                K.gemm(a3, l["qkv_w3"], l["qkv_b"], heads=heads, split_k=True, a_planes=planes)
-                K.attention(q, k, vt, o3, Bq=B, H=H, Nq=T, Nk=T, Tq_cap=T, Tk_cap=T, NP=NP, causal=causal, kv_len=kv_len, split3=True)
-            K.gemm(o3, l["o_w3"], l["o_b"], out=x, resid=x, split_k=True, a_planes=planes if f32_attn else 3)
-            K.layernorm(x, l["n2g"], l["n2b"], eps, out16=a3, split3=True, planes=planes)
-            K.gemm(a3, l["fc1_w3"], l["fc1_b"], split3_out=hid3, act=K.ACT_QUICK_GELU, split_k=True, split3_planes=planes, a_planes=planes)
-            K.gemm(hid3, l["fc2_w3"], l["fc2_b"], out=x, resid=x, split_k=True, a_planes=planes)
-        return x
-    stats = torch.empty((M, D // 64, 2), dtype=torch.float32, device=dev) if "fc1_f" in layers[0] else None
-    if "qkv_w8" in layers[0] and T > 32:
-        xn8 = torch.empty((M, D), dtype=FP8, device=dev)
-        o8 = torch.empty((M, D), dtype=FP8, device=dev)
-        hid8 = torch.empty((M, layers[0]["fc1_w8"].shape[0]), dtype=FP8, device=dev)
-        for l in layers:
-            K.layernorm(x, l["n1g"], l["n1b"], eps, out16=xn8)
-            K.gemm(xn8, l["qkv_w8"], l["qkv_b"], heads=heads, w_scale=l["qkv_s"])
-            K.attention(q, k, vt, o8, Bq=B, H=H, Nq=T, Nk=T, Tq_cap=T, Tk_cap=T, NP=NP, causal=causal, kv_len=kv_len)
-            K.gemm(o8, l["o_w8"], l["o_b"], out=x, resid=x, w_scale=l["o_s"], dtype16=cdt)
-            K.layernorm(x, l["n2g"], l["n2b"], eps, out16=xn8)
-            K.gemm(xn8, l["fc1_w8"], l["fc1_b"], out=hid8, act=K.ACT_QUICK_GELU, w_scale=l["fc1_s"], dtype16=cdt)
-            K.gemm(hid8, l["fc2_w8"], l["fc2_b"], out=x, resid=x, w_scale=l["fc2_s"], dtype16=cdt)
-        return x
-    for i, l in enumerate(layers):
-        fused = "fc1_f" in l      # LayerNorm folded into the consuming GEMMs (see vit.VisionTransformer.run_blocks)
-        if fused and i > 0:
-            w_, b_, cs = l["qkv_f"]
-            K.gemm(xn, w_, b_, heads=heads, ln=(cs, eps, stats))
-        else:
-            K.layernorm(x, l["n1g"], l["n1b"], eps, out16=xn)
-            K.gemm(xn, l["qkv_w"], l["qkv_b"], heads=heads)
-        K.attention(q, k, vt, o, Bq=B, H=H, Nq=T, Nk=T, Tq_cap=T, Tk_cap=T, NP=NP, causal=causal, kv_len=kv_len)
-        if fused:
-            K.gemm(o, l["o_w"], l["o_b"], out=x, resid=x, out16=xn, ln_stats_out=stats)
-            w_, b_, cs = l["fc1_f"]
-            K.gemm(xn, w_, b_, out=hid, act=K.ACT_QUICK_GELU, ln=(cs, eps, stats))
-            K.gemm(hid, l["fc2_w"], l["fc2_b"], out=x, resid=x, out16=xn if i + 1 < n else None,
-                   ln_stats_out=stats if i + 1 < n else None)
-        else:
-            K.gemm(o, l["o_w"], l["o_b"], out=x, resid=x)
-            K.layernorm(x, l["n2g"], l["n2b"], eps, out16=xn)
-            K.gemm(xn, l["fc1_w"], l["fc1_b"], out=hid, act=K.ACT_QUICK_GELU)
-            K.gemm(hid, l["fc2_w"], l["fc2_b"], out=x, resid=x)
-    return x
 
 
 class CLIPModel(PackedCache, nn.Module):
@@ -278,8 +147,8 @@ class CLIPModel(PackedCache, nn.Module):
         self.logit_scale = nn.Parameter(torch.tensor(2.6592))
         import os
         self.fuse_layernorm = os.environ.get("VIDIL_FUSE_LN", "1") != "0"   # vision tower only (the text tower runs once per ontology)
-        # (parity precision mode: the vision tower's last layer on the class-token rows only — _run_layers(cls_last=True); A/B switch)
-        self.cls_only_last_layer = os.environ.get("VIDIL_CLIP_CLS_LAST", "1") != "0"
+        # (parity precision mode: the vision tower's last layer on the class-token rows only — tower.run_layers(cls_last=True))
+        self.cls_only_last_layer = True
         self.apply(self._init)
 
     @classmethod
@@ -350,11 +219,11 @@ class CLIPModel(PackedCache, nn.Module):
             pre_g=v32(vm.pre_layrnorm.weight), pre_b=v32(vm.pre_layrnorm.bias),
             post_g=v32(vm.post_layernorm.weight), post_b=v32(vm.post_layernorm.bias),
             vproj=w16(self.visual_projection.weight, dtype=c),
-            vlayers=_pack_layers(vm.encoder, c, self.fuse_layernorm and not par, self.fp8 and not par, par),
+            vlayers=_pack_layers(vm.encoder, c, "parity" if par else "fp8" if self.fp8 else "fold" if self.fuse_layernorm else "plain"),
             tok=v32(tm.embeddings.token_embedding.weight).view(self.config.text_config.vocab_size, -1),
             tpos=v32(tm.embeddings.position_embedding.weight).view(self.config.text_config.max_position_embeddings, -1),
             fin_g=v32(tm.final_layer_norm.weight), fin_b=v32(tm.final_layer_norm.bias),
-            tproj=w16(self.text_projection.weight, dtype=c), tlayers=_pack_layers(tm.encoder, c, parity=par))
+            tproj=w16(self.text_projection.weight, dtype=c), tlayers=_pack_layers(tm.encoder, c, "parity" if par else "plain"))
 
     # ------------------------------------------------------------------ vision tower
     def _vision_from_patches(self, patches16, B, pooled=False):
@@ -371,8 +240,9 @@ class CLIPModel(PackedCache, nn.Module):
         K.set_cls_row(x, p["cls"], p["pos"], B, T, D)
         K.layernorm(x, p["pre_g"], p["pre_b"], vc.layer_norm_eps, out32=x)
         cls_last = par and self.cls_only_last_layer
-        xo = _run_layers(p["vlayers"], x, B, T, H, vc.layer_norm_eps, f32_attn=parity_attention_f32(self), arith=parity_attention_arith(self),
-                         cls_last=cls_last)
+        # (fp8 operands only with the LDS-staged attention: 32 tokens or fewer run on the plain weights)
+        xo, _ = run_layers(p["vlayers"], x, B, T, H, vc.layer_norm_eps, K.ACT_QUICK_GELU, parity=par, fp8="qkv_w8" in p["vlayers"][0] and T > 32,
+                           f32_attn=parity_attention_f32(self), arith=parity_attention_arith(self), cls_last=cls_last)
         cls_rows = xo.shape[0] == B and T > 1          # (the layers handed back the class-token rows [B, D] instead of the stream)
         pooled16 = torch.empty((B, (3 if par else 1) * D), dtype=cdt, device=dev)
         pooled32 = torch.empty((B, D), dtype=torch.float32, device=dev) if pooled else None
@@ -427,8 +297,8 @@ class CLIPModel(PackedCache, nn.Module):
         kv_len = None
         if attention_mask is not None:
             kv_len = attention_mask.to(dev).sum(dim=1).to(torch.int32).contiguous()
-        _run_layers(p["tlayers"], x, N, L, H, tc.layer_norm_eps, causal=True, kv_len=kv_len, f32_attn=parity_attention_f32(self),
-                    arith=parity_attention_arith(self))
+        run_layers(p["tlayers"], x, N, L, H, tc.layer_norm_eps, K.ACT_QUICK_GELU, causal=True, kv_len=kv_len, parity=p["parity"],
+                   f32_attn=parity_attention_f32(self), arith=parity_attention_arith(self))
         if tc.eos_token_id == 2:
             pos = ids32.argmax(dim=-1)
         else:

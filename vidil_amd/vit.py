@@ -17,6 +17,8 @@ stand-alone LayerNorm kernels —
 
 with the residual stream, LayerNorm statistics and softmax in f32 and the MFMA
 operands in the model's compute dtype (f16 or bf16, packing.set_compute_dtype).
+The blocks are packed and run by tower.py (shared with the CLIP towers), which also holds
+the fp8 and parity forms of the block.
 """
 from __future__ import annotations
 
@@ -27,7 +29,8 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .packing import FP8, PackedCache, fold_layernorm, require_cuda, v32, w3, w3_patch, w8, w16, w16_patch, parity_attention_arith, parity_attention_f32, parity_attention_kind
+from .packing import PackedCache, require_cuda, v32, w3_patch, w16_patch, parity_attention_arith, parity_attention_f32, parity_attention_kind
+from .tower import pack_layer, run_layers
 
 
 class PatchEmbed(nn.Module):
@@ -130,34 +133,15 @@ class VisionTransformer(PackedCache, nn.Module):
             pe_w=w16_patch(pe.weight, c), pe_b=v32(pe.bias),
             cls=v32(self.cls_token), pos=v32(self.pos_embed).view(-1, D),
             norm_g=v32(self.norm.weight), norm_b=v32(self.norm.bias), blocks=[])
+        wb = lambda m: (m.weight, m.bias)
+        k_par = self.parity_last_blocks
         for i, b in enumerate(self.blocks):
-            d = dict(
-                n1g=v32(b.norm1.weight), n1b=v32(b.norm1.bias),
-                qkv_w=w16(b.attn.qkv.weight, dtype=c), qkv_b=v32(b.attn.qkv.bias),
-                proj_w=w16(b.attn.proj.weight, dtype=c), proj_b=v32(b.attn.proj.bias),
-                n2g=v32(b.norm2.weight), n2b=v32(b.norm2.bias),
-                fc1_w=w16(b.mlp.fc1.weight, dtype=c), fc1_b=v32(b.mlp.fc1.bias),
-                fc2_w=w16(b.mlp.fc2.weight, dtype=c), fc2_b=v32(b.mlp.fc2.bias))
-            if self.parity:
-                # parity precision mode (packing.set_parity_mode): [W_hi | W_hi | W_lo] against [x_hi | x_lo | x_hi] rows
-                # (mixed form: only the last parity_last_blocks blocks; the others keep their plain operands)
-                k_par = self.parity_last_blocks
-                if k_par is None or i >= len(self.blocks) - k_par:
-                    for name, lin in (("qkv", b.attn.qkv), ("proj", b.attn.proj), ("fc1", b.mlp.fc1), ("fc2", b.mlp.fc2)):
-                        d[name + "_w3"] = w3(lin.weight, dtype=c)
-            elif self.fp8:
-                # fp8 tower mode: the four big GEMMs on e4m3 operands (weights per-output-row scaled), LayerNorm as
-                # a stand-alone kernel writing fp8 (its output is well scaled; the raw stream is not)
-                for name, lin in (("qkv", b.attn.qkv), ("proj", b.attn.proj), ("fc1", b.mlp.fc1), ("fc2", b.mlp.fc2)):
-                    d[name + "_w8"], d[name + "_s"] = w8(lin.weight)
-            elif self.fuse_layernorm:
-                # norm2 folded into fc1 in every block; norm1 folded into qkv from block 1 on (block 0's input comes
-                # from the patch-embedding GEMM, which writes no 16-bit copy of the stream)
-                d["fc1_f"] = fold_layernorm(b.mlp.fc1.weight, b.mlp.fc1.bias, b.norm2.weight, b.norm2.bias, c)
-                if i > 0:
-                    d["qkv_f"] = fold_layernorm(b.attn.qkv.weight, b.attn.qkv.bias, b.norm1.weight, b.norm1.bias, c)
-            p["blocks"].append(d)
-        p["fused"] = self.fuse_layernorm and not self.fp8 and not self.parity
+            if self.parity:     # (mixed form: only the last parity_last_blocks blocks; the others keep their plain operands)
+                form = "parity" if k_par is None or i >= len(self.blocks) - k_par else "plain"
+            else:
+                form = "fp8" if self.fp8 else "fold" if self.fuse_layernorm else "plain"
+            p["blocks"].append(pack_layer(wb(b.norm1), (b.attn.qkv.weight,), (b.attn.qkv.bias,), wb(b.attn.proj), wb(b.norm2),
+                                          wb(b.mlp.fc1), wb(b.mlp.fc2), dtype=c, form=form, fold_qkv=i > 0))
         p["fp8"] = self.fp8
         p["parity"] = self.parity
         if self.parity:
@@ -177,139 +161,22 @@ class VisionTransformer(PackedCache, nn.Module):
         return x
 
     def run_blocks(self, x, B, want16=True):
-        """x: f32 [B*T, D] residual stream (modified in place).  Returns (y32, y16) after the final LN."""
+        """x: f32 [B*T, D] residual stream (modified in place).  Returns (y32, y16) after the final LN; in the parity precision
+        mode y16 is [M, 3D]: the [hi | lo | hi] split rows of the final LayerNorm (the cross K|V projection's operand)."""
         p = self.packed()
-        D, H = self.embed_dim, self.num_heads
         T = self.patch_embed.num_patches + 1
-        # V stays row-major (NP = 0): the QKV GEMM stores it like K with 16-B stores and the staged attention kernel
-        # transposes it on the way into LDS — cheaper than scattering V^T from the GEMM epilogue (T > 32 rows here)
-        NP = 0 if T > 32 else (T + 15) // 16 * 16     # (tiny test geometries fall back to V^T + the direct kernels)
-        dev = x.device
-        M = B * T
-        cdt = p["pe_w"].dtype
-        xn = torch.empty((M, D), dtype=cdt, device=dev)
-        q = torch.empty((B, H, T, 64), dtype=cdt, device=dev)
-        k = torch.empty((B, H, T, 64), dtype=cdt, device=dev)
-        vt = torch.empty((B, H, T, 64) if NP == 0 else (B, H, 64, NP), dtype=cdt, device=dev)
-        o = torch.empty((M, D), dtype=cdt, device=dev)
-        hid = torch.empty((M, p["blocks"][0]["fc1_w"].shape[0]), dtype=cdt, device=dev)
-        heads = dict(q=q, k=k, vt=vt, T=T, H=H, part0=0, t_off=0, Tq_cap=T, Tk_cap=T, NP=NP, q_scale=0.125)
-        if p.get("parity"):
-            return self._run_blocks_parity(p, x, B, T, q, k, vt, heads, NP, want16)
-        if p.get("fp8"):
-            return self._run_blocks_fp8(p, x, B, T, q, k, vt, heads, NP, want16)
-        # Fused LayerNorm (models/vit.py:107-110): the residual GEMMs (proj, fc2) also store the stream in the operand
-        # type (``xn`` then holds RAW x, not LN(x)) and the next GEMM applies the LayerNorm to its accumulators.
-        fused = p.get("fused", False)
-        nblk = len(p["blocks"])
-        stats = torch.empty((M, D // 64, 2), dtype=torch.float32, device=dev) if fused else None
-        for i, b in enumerate(p["blocks"]):
-            if fused and i > 0:
-                w_, b_, cs = b["qkv_f"]
-                K.gemm(xn, w_, b_, heads=heads, ln=(cs, self.ln_eps, stats))
-            else:
-                K.layernorm(x, b["n1g"], b["n1b"], self.ln_eps, out16=xn)
-                K.gemm(xn, b["qkv_w"], b["qkv_b"], heads=heads)
-            K.attention(q, k, vt, o, Bq=B, H=H, Nq=T, Nk=T, Tq_cap=T, Tk_cap=T, NP=NP)
-            if fused:
-                K.gemm(o, b["proj_w"], b["proj_b"], out=x, resid=x, out16=xn, ln_stats_out=stats)
-                w_, b_, cs = b["fc1_f"]
-                K.gemm(xn, w_, b_, out=hid, act=K.ACT_GELU_ERF, ln=(cs, self.ln_eps, stats))
-                K.gemm(hid, b["fc2_w"], b["fc2_b"], out=x, resid=x, out16=xn if i + 1 < nblk else None,
-                       ln_stats_out=stats if i + 1 < nblk else None)
-            else:
-                K.gemm(o, b["proj_w"], b["proj_b"], out=x, resid=x)
-                K.layernorm(x, b["n2g"], b["n2b"], self.ln_eps, out16=xn)
-                K.gemm(xn, b["fc1_w"], b["fc1_b"], out=hid, act=K.ACT_GELU_ERF)
-                K.gemm(hid, b["fc2_w"], b["fc2_b"], out=x, resid=x)
-        y32 = torch.empty((M, D), dtype=torch.float32, device=dev)
-        y16 = xn if want16 else None
-        K.layernorm(x, p["norm_g"], p["norm_b"], self.ln_eps, out16=y16, out32=y32)
-        return y32, y16
-
-    def _run_blocks_parity(self, p, x, B, T, q, k, vt, heads, NP, want16):
-        """Parity precision mode: the same block sequence with every GEMM on error-compensated operands (K tripled):
-        LayerNorm and attention write [hi | lo | hi] rows directly (VIDIL_DT_SPLIT3), the GELU output goes through f32
-        and vidil_split3_f32.  Returns (y32, y3) with y3 = [M, 3D] split rows of the final LayerNorm (the cross K|V
-        projection's operand).  ~3x the MFMA work of the plain path.  Attention (packing.set_parity_attention): "split" / "f32" —
-        Q | K | V stay f32 rows of the projection GEMM's output and vidil_attention_f32 reads them in place (split-operand MFMA
-        or f32 arithmetic); "16" — the per-head scatter and the 16-bit kernels, Q / K / V and the probabilities rounded to 16 bits."""
-        D, H = self.embed_dim, self.num_heads
-        dev, cdt = x.device, q.dtype
-        M = B * T
-        Dh = p["blocks"][0]["fc1_w"].shape[0]
-        a3 = torch.empty((M, 3 * D), dtype=cdt, device=dev)
-        o3 = torch.empty((M, 3 * D), dtype=cdt, device=dev)
-        hid3 = torch.empty((M, 3 * Dh), dtype=cdt, device=dev)
-        # (a consumer that takes the K-loop form of the compensated product reads planes hi | lo of its operand rows only, so their
-        #  producer need not write the third — decided per CALL from the blocks' actual consumers (ADVICE r5: e.g. the per-head
-        #  epilogue with fewer than 8 tokens runs the plain K = 3 Kl product); the
-        #  consumers then state a_planes, so a launch that would read an unwritten plane fails instead of computing on it)
-        f32_attn, arith = parity_attention_f32(self), parity_attention_arith(self)
-        qkv32 = torch.empty((M, 3 * D), dtype=torch.float32, device=dev) if f32_attn else None
-        b3 = next((b for b in p["blocks"] if "qkv_w3" in b), None)
-        planes = 3
-        if b3 is not None:
-            qkv_kw = dict(out=qkv32) if f32_attn else dict(heads=heads)
-            if (K.split_k_serves(a3, b3["qkv_w3"], b3["qkv_b"], **qkv_kw) and K.split_k_serves(o3, b3["proj_w3"], b3["proj_b"], out=x, resid=x)
-                    and K.split_k_serves(a3, b3["fc1_w3"], b3["fc1_b"], split3_out=hid3, act=K.ACT_GELU_ERF)
-                    and K.split_k_serves(hid3, b3["fc2_w3"], b3["fc2_b"], out=x, resid=x)):
-                planes = 2
-        K.poison_third_plane(planes, a3, o3, hid3)
-        plain = [b for b in p["blocks"] if "qkv_w3" not in b]
-        if plain:       # mixed form: the leading blocks on plain 16-bit operands (unfused: LayerNorm kernel + plain GEMM)
-            xn = torch.empty((M, D), dtype=cdt, device=dev)
-            o = torch.empty((M, D), dtype=cdt, device=dev)
-            hid = torch.empty((M, Dh), dtype=cdt, device=dev)
-        for b in p["blocks"]:
-            if "qkv_w3" not in b:
-                K.layernorm(x, b["n1g"], b["n1b"], self.ln_eps, out16=xn)
-                K.gemm(xn, b["qkv_w"], b["qkv_b"], heads=heads)
-                K.attention(q, k, vt, o, Bq=B, H=H, Nq=T, Nk=T, Tq_cap=T, Tk_cap=T, NP=NP)
-                K.gemm(o, b["proj_w"], b["proj_b"], out=x, resid=x)
-                K.layernorm(x, b["n2g"], b["n2b"], self.ln_eps, out16=xn)
-                K.gemm(xn, b["fc1_w"], b["fc1_b"], out=hid, act=K.ACT_GELU_ERF)
-                K.gemm(hid, b["fc2_w"], b["fc2_b"], out=x, resid=x)
-                continue
-            K.layernorm(x, b["n1g"], b["n1b"], self.ln_eps, out16=a3, split3=True, planes=planes)
-            if f32_attn:    # Q | K | V stay f32 and row-major; the f32 attention reads them in place (no per-head scatter)
-                K.gemm(a3, b["qkv_w3"], b["qkv_b"], out=qkv32, split_k=True, a_planes=planes)
-                K.attention_f32(qkv32[:, :D], qkv32[:, D:2 * D], qkv32[:, 2 * D:], o3, Bq=B, H=H, Nq=T, Nk=T, arith=arith, planes=planes)
-            else:
-                K.gemm(a3, b["qkv_w3"], b["qkv_b"], heads=heads, split_k=True, a_planes=planes)
-                K.attention(q, k, vt, o3, Bq=B, H=H, Nq=T, Nk=T, Tq_cap=T, Tk_cap=T, NP=NP, split3=True)      # (writes all three planes)
-            K.gemm(o3, b["proj_w3"], b["proj_b"], out=x, resid=x, split_k=True, a_planes=planes if f32_attn else 3)
-            K.layernorm(x, b["n2g"], b["n2b"], self.ln_eps, out16=a3, split3=True, planes=planes)
-            # (fc1 + erf-GELU in f32, handed to fc2 as [hi | lo | hi] rows by the GEMM's own epilogue: no f32 round trip)
-            K.gemm(a3, b["fc1_w3"], b["fc1_b"], split3_out=hid3, act=K.ACT_GELU_ERF, split_k=True, split3_planes=planes, a_planes=planes)
-            K.gemm(hid3, b["fc2_w3"], b["fc2_b"], out=x, resid=x, split_k=True, a_planes=planes)
-        y32 = torch.empty((M, D), dtype=torch.float32, device=dev)
-        # (the image tokens leave this module: their consumer — BertModel.project_cross_kv, any epilogue, any token count — is not
-        #  known here, so all three planes are written: one launch per forward)
-        K.layernorm(x, p["norm_g"], p["norm_b"], self.ln_eps, out16=a3 if want16 else None, out32=y32, split3=True, planes=3)
-        return y32, (a3 if want16 else None)
-
-    def _run_blocks_fp8(self, p, x, B, T, q, k, vt, heads, NP, want16):
-        """fp8 tower mode (BASELINE config 5): LN -> fp8, QKV / proj / fc1 / fc2 on e4m3 operands at twice the 16-bit
-        MFMA rate, attention on the 16-bit companion type writing fp8, f32 residual stream.  NOT a parity mode: e4m3
-        carries 3 mantissa bits (tests/test_fp8_gpu.py states the measured deviation from the fp32 oracle)."""
-        D, H = self.embed_dim, self.num_heads
-        dev = x.device
-        M = B * T
-        xn8 = torch.empty((M, D), dtype=FP8, device=dev)
-        o8 = torch.empty((M, D), dtype=FP8, device=dev)
-        hid8 = torch.empty((M, p["blocks"][0]["fc1_w8"].shape[0]), dtype=FP8, device=dev)
-        for b in p["blocks"]:
-            K.layernorm(x, b["n1g"], b["n1b"], self.ln_eps, out16=xn8)
-            K.gemm(xn8, b["qkv_w8"], b["qkv_b"], heads=heads, w_scale=b["qkv_s"])
-            K.attention(q, k, vt, o8, Bq=B, H=H, Nq=T, Nk=T, Tq_cap=T, Tk_cap=T, NP=NP)
-            K.gemm(o8, b["proj_w8"], b["proj_b"], out=x, resid=x, w_scale=b["proj_s"], dtype16=q.dtype)
-            K.layernorm(x, b["n2g"], b["n2b"], self.ln_eps, out16=xn8)
-            K.gemm(xn8, b["fc1_w8"], b["fc1_b"], out=hid8, act=K.ACT_GELU_ERF, w_scale=b["fc1_s"], dtype16=q.dtype)
-            K.gemm(hid8, b["fc2_w8"], b["fc2_b"], out=x, resid=x, w_scale=b["fc2_s"], dtype16=q.dtype)
-        y32 = torch.empty((M, D), dtype=torch.float32, device=dev)
-        y16 = torch.empty((M, D), dtype=q.dtype, device=dev) if want16 else None
-        K.layernorm(x, p["norm_g"], p["norm_b"], self.ln_eps, out16=y16, out32=y32)
+        par = p["parity"]
+        _, y16 = run_layers(p["blocks"], x, B, T, self.num_heads, self.ln_eps, K.ACT_GELU_ERF, parity=par, fp8=p["fp8"],
+                            f32_attn=parity_attention_f32(self), arith=parity_attention_arith(self))
+        # the final LayerNorm writes its 16-bit rows into the layers' operand buffer (the fp8 form has none of that type: a fresh one)
+        if not want16:
+            y16 = None
+        elif y16 is None:
+            y16 = torch.empty(x.shape, dtype=self.cdt, device=x.device)
+        y32 = torch.empty_like(x)
+        # (parity: the image tokens leave this module: their consumer — BertModel.project_cross_kv, any epilogue, any token count
+        #  — is not known here, so all three planes are written: one launch per forward)
+        K.layernorm(x, p["norm_g"], p["norm_b"], self.ln_eps, out16=y16, out32=y32, split3=par, planes=3)
         return y32, y16
 
     def forward_both(self, x):
