@@ -523,6 +523,8 @@ int vidil_scan_topk(const float* img, const float* txt, int32_t NF, int32_t D,
 /*     same exact k-ordered f32 chain as vidil_scan_topk;                      */
 /*   vidil_topk_rows: the k (<= 128) largest of each of R rows of N (<= 38400)  */
 /*     values, sorted by (value desc, index asc): out_v f32 [R,k], out_i i32.  */
+/*     -inf is no winner: a row with fewer than k values above it ends in      */
+/*     -inf / -1.                                                              */
 /* ------------------------------------------------------------------------ */
 int vidil_scan_scores(const float* img, const float* txt, int32_t NF, int32_t D,
                       int32_t NC, float* out, void* stream);

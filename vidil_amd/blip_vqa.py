@@ -156,6 +156,8 @@ class BLIP_VQA(nn.Module):
         lp = self.first_token_logprobs(states16, Q, q_lens, answer_ids)
         _, topk_ids = K.topk_rows(lp, k)                       # (value descending, index ascending; k <= 128, A <= 38,400)
         pick = topk_ids.cpu().long().view(-1)
+        if bool((pick < 0).any()):                             # (topk_rows: -1 where a row has fewer than k values above -inf)
+            raise ValueError(f"BLIP_VQA rank: a question has fewer than k_test={k} answers whose first token has a finite log-probability")
         res = self.text_decoder.score(states16, Q, answer_ids[pick], answer_lens[pick],
                                       image_index=torch.arange(Q).repeat_interleave(k), label_smoothing=VQA_LABEL_SMOOTHING,
                                       prompt_length=1, cross_kv_len=q_lens)

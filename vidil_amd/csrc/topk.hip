@@ -25,7 +25,12 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
   __syncthreads();
   for (int it = 0; it < k; ++it) {
     Best me{-INFINITY, 0x7fffffff};
-    for (int i = tid; i < N; i += 256) me = better(me, Best{row[i], i});
+    // (-inf is no winner: `better` would let an element at -inf beat the empty {-inf, 0x7fffffff} on the index, and a row with
+    //  fewer than k finite values then repeated the index of its first -inf element k times instead of the -1 tail below)
+    for (int i = tid; i < N; i += 256) {
+      const float v = row[i];
+      if (v != -INFINITY) me = better(me, Best{v, i});
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) me = better(me, Best{__shfl_xor(me.v, o, 64), __shfl_xor(me.i, o, 64)});
     if ((tid & 63) == 0) wbest[tid >> 6] = me;

@@ -616,7 +616,8 @@ def scan_scores(img, txt):
 
 
 def topk_rows(x, k):
-    """Sorted top-k of every row of f32 [R,N] (value desc, index asc): (values f32 [R,k], indices i32 [R,k])."""
+    """Sorted top-k of every row of f32 [R,N] (value desc, index asc): (values f32 [R,k], indices i32 [R,k]).  -inf is no
+    winner: a row with fewer than k values above it ends in -inf / -1."""
     if x.dim() != 2 or x.stride(1) != 1:
         raise VidilHipError(f"topk_rows: expected a 2-D f32 tensor with contiguous rows, got {tuple(x.shape)} strides {x.stride()}")
     R, N = x.shape
