@@ -196,7 +196,15 @@ int vidil_layernorm(const float* x, int64_t x_stride, const float* gamma,
                     void* out16, int32_t dtype16, float* out_f32, void* stream);
 
 /* ------------------------------------------------------------------------ */
-/* Attention for short sequences (Nk <= 768): softmax(Q K^T [+mask]) V.       */
+/* Attention: softmax(Q K^T [+mask]) V.  Nk <= 768 in every form below; 768 <   */
+/* Nk <= 16384 (a video's frames concatenated as one encoder sequence) in the  */
+/* LONG-KEY form (csrc/attention.hip: attn_long_kernel), which serves launches */
+/* with more than 32 query rows per unit (max_group*Nq, kv_group*Nq, or Nq     */
+/* with kv_index), kv_tiled == 0, causal == 0 and out_dtype == dtype, with      */
+/* row-major V or V^T, all three unit forms and kv_len; every other launch over */
+/* 768 keys returns VIDIL_EUNSUP.  max_group is an upper bound: row tiles past  */
+/* a unit's last row return at once.  A row's bits there depend on its Q row,   */
+/* the unit's K / V and its key limit alone, not on the launch around it.       */
 /* Q  T16 [Bq][H][Tq_cap][64] (already scaled by 1/sqrt(64)),                 */
 /* K  T16 [Bk][H][Tk_cap][64], VT T16 [Bk][H][64][NP] with NP % 16 == 0 and    */
 /* the key axis of every 16-key block permuted to 0-3, 8-11, 4-7, 12-15 (the   */

@@ -113,18 +113,23 @@ class BLIP_ITM(PackedCache, nn.Module):
         frames (``cross=``).  ``min_rows_per_image``: the smallest number of query rows a launch will present per
         image — row-major V (cheaper stores) is only readable by the staged kernel, i.e. above 32 rows."""
         Te = enc16.shape[0] // n_images
-        return self.text_encoder.project_cross_kv(enc16, n_images, Te, v_rowmajor=min_rows_per_image > 32,
+        # (over BertModel.LONG_KEYS tokens per image — a video's concatenated frames — every launch is rounded up past 32 rows)
+        return self.text_encoder.project_cross_kv(enc16, n_images, Te,
+                                                  v_rowmajor=min_rows_per_image > 32 or Te > self.text_encoder.LONG_KEYS,
                                                   last_layer_vt=True)
 
     @torch.no_grad()
     def itm_pairs(self, enc16, n_images, ids, lens, image_index=None, group_start=None, max_group=0, pair_text=None,
-                  cross=None):
+                  cross=None, t_eff=None):
         """enc16 f16 [n_images*Te, width]; ids i32 [P,35]; lens i32 [P].  Either image_index i32 [P] (pair ->
         image, any order) or, for IMAGE-MAJOR pair order, group_start i32 [n_images+1] (pairs of image j are
         group_start[j] .. group_start[j+1]-1, at most max_group of them), which lets one fetch of an image's
         cross K/V serve all its captions.  pair_text (int [P]): ids / lens then hold the U DISTINCT texts and pair p
         scores text pair_text[p] — the text-only front of the encoder runs once per text (BertModel.encode_cls).
         cross: ``project_image_kv``'s result for these images when several calls score pairs of the same frames.
+        t_eff: the token count every text is cut to (default: this call's longest text) — a caller that scores one set of pairs
+        in several calls passes the longest text of ALL of them, so that a pair's launches do not depend on its call.
+        More than BertModel.LONG_KEYS tokens per image (a video as one image of N*T tokens) need the group_start form.
         Returns f32 [P,2] raw ITM logits."""
         require_cuda(enc16, "BLIP_ITM")
         te = self.text_encoder
@@ -133,13 +138,20 @@ class BLIP_ITM(PackedCache, nn.Module):
         # The reference pads every caption to 35 tokens (models/blip_itm.py:46).  Padded keys are masked and a
         # padded row never feeds a real one, so the [CLS] output is unchanged if the batch is cut to its
         # longest real caption; this removes the all-padding columns.
-        t_eff = min(ids.shape[1], int(lens.max().item())) if ids.shape[0] else ids.shape[1]
+        if t_eff is None:
+            t_eff = min(ids.shape[1], int(lens.max().item())) if ids.shape[0] else ids.shape[1]
+        elif not 1 <= t_eff <= ids.shape[1] or (ids.shape[0] and int(lens.max().item()) > t_eff):
+            raise K.VidilHipError(f"itm_pairs: t_eff={t_eff} must cover the longest text and fit ids' {ids.shape[1]} columns")
         # image-major groups with more than 32 query rows go through the staged attention kernel, which takes V
         # row-major (plain 16-B stores from the K|V GEMM instead of the V^T scatter)
         rows_per_image = (max_group if group_start is not None else 1) * t_eff
+        long_keys = Te > te.LONG_KEYS        # (BertModel._cross_bound then rounds every launch's bound up past 32 rows)
+        if long_keys and group_start is None:
+            raise K.VidilHipError(f"itm_pairs: {Te} > {te.LONG_KEYS} tokens per image need image-major pairs: use group_start "
+                                  "(the image_index form has one pair's rows per unit)")
         if cross is None:
-            cross = te.project_cross_kv(enc16, n_images, Te, v_rowmajor=rows_per_image > 32, last_layer_vt=True)
-        elif cross.NP == 0 and rows_per_image <= 32:
+            cross = te.project_cross_kv(enc16, n_images, Te, v_rowmajor=rows_per_image > 32 or long_keys, last_layer_vt=True)
+        elif cross.NP == 0 and rows_per_image <= 32 and not long_keys:
             raise K.VidilHipError("itm_pairs: cross= holds row-major values but this call has at most 32 query rows "
                                   "per image (project_image_kv(min_rows_per_image=...))")
         ids = ids[:, :t_eff].to(dev).contiguous()

@@ -10,6 +10,11 @@ reference's own factory, which only prints the missing keys).  What the tokenize
   * ``text_features(texts)``       -> unit-norm ``normalize(text_proj(text_encoder(ids, mode='text')[:,0]))`` plus the
     ids (first token replaced by [ENC]) and lengths for the re-rank    (get_text_embeddings_blip, :113-133)
   * ``rerank(...)``                -> ``itm_head(text_encoder(ids, image)[:,0])[:,1]`` for (frame, text) pairs (:283-292)
+
+and, for the video-level retrieval evaluation (eval_retrieval_video.py; vidil_amd/video_retrieval.py):
+
+  * ``video_features_u8(frames)``  -> the tokens of every frame, a video's N*T rows contiguous, and
+    ``normalize(mean_frames(vision_proj(cls)))``                       (eval_retrieval_video.py:61-69)
 """
 from __future__ import annotations
 
@@ -57,6 +62,40 @@ class BLIP_Retrieval(BLIP_ITM):
         N = image.shape[0]
         y32, y16 = self.visual_encoder.forward_both(image)
         return y16, self.image_embeds(y32, y16, N)
+
+    # ------------------------------------------------------------------ video level (eval_retrieval_video.py:59-71)
+    def _video_embeds(self, y16, B, N):
+        """normalize(mean over the N frames of vision_proj(frame [CLS])): the UN-normalised projections are averaged, then
+        normalised once (eval_retrieval_video.py:65-67) -> f32 [B, embed_dim]."""
+        p = self.packed()
+        if p["parity"]:
+            raise K.VidilHipError("BLIP_Retrieval: the video-level features are not built for the parity precision mode")
+        T, C = y16.shape[0] // (B * N), y16.shape[-1]
+        proj = torch.empty((B * N, p["vp_w"].shape[0]), dtype=torch.float32, device=y16.device)
+        K.gemm(y16.view(-1), p["vp_w"], p["vp_b"], out=proj, M=B * N, lda=T * C)
+        return K.l2_normalize_rows(proj.view(B, N, -1).mean(dim=1).contiguous())
+
+    @torch.no_grad()
+    def video_features_u8(self, frames_u8):
+        """uint8 [B,N,S,S,3] -> (frame tokens 16-bit [B*N*T, width], unit-norm video embeddings f32 [B, embed_dim]).  A video's
+        N*T token rows are contiguous: as encoder states it is ONE image of N*T tokens (``video_feat.view(B, -1, C)``,
+        eval_retrieval_video.py:69; ``itm_pairs(tokens, B, ...)``)."""
+        require_cuda(frames_u8, "BLIP_Retrieval.video_features_u8")
+        if frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
+            raise K.VidilHipError(f"video_features_u8: uint8 [B,N,S,S,3] expected, got {tuple(frames_u8.shape)}")
+        B, N = frames_u8.shape[:2]
+        _, y16 = self.visual_encoder.forward_u8(frames_u8.reshape(B * N, *frames_u8.shape[2:]), CLIP_MEAN, CLIP_STD)
+        return y16, self._video_embeds(y16, B, N)
+
+    @torch.no_grad()
+    def video_features(self, video):
+        """f32 [B,N,3,S,S] (normalised) -> same as video_features_u8 (eval_retrieval_video.py:61-69)."""
+        require_cuda(video, "BLIP_Retrieval.video_features")
+        if video.dim() != 5 or video.shape[2] != 3:
+            raise K.VidilHipError(f"video_features: f32 [B,N,3,S,S] expected, got {tuple(video.shape)}")
+        B, N = video.shape[:2]
+        _, y16 = self.visual_encoder.forward_both(video.reshape(B * N, *video.shape[2:]))
+        return y16, self._video_embeds(y16, B, N)
 
     @torch.no_grad()
     def text_features(self, texts, device, batch=512):

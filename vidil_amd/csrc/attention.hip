@@ -1,6 +1,8 @@
 // attention.hip — softmax(Q K^T) V for the short sequences on this path
 // (ViT 197 keys, CLIP 50/77/257, MED text 1..35 queries over <=20 cached or 197
-// image keys).
+// image keys; Nk <= 768), and for the long encoder sequences of the video-level
+// heads (N frames x 197 / 577 tokens as ONE sequence, 768 < Nk <= 16384:
+// attn_long_kernel, more than 32 query rows per unit).
 //
 // Work unit = (key/value batch j, head h): all query batches that read j's K/V
 // (uniform groups of `kv_group` consecutive query batches, or an explicit prefix
@@ -562,6 +564,187 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void attn_lds_kernel(cons
     else
       store_rows(p, ri, h, O, l > 0.f ? 1.0f / l : 0.f);
   }
+}
+
+// ------------------------------------------------------------------ long-key staged kernel (Nk > 768)
+// A video's frames concatenated as ONE encoder sequence (8 x 577 = 4,616 keys, 16 x 577 = 9,232) are tens of chunks for the
+// kernel above, whose further chunks are staged serially between two barriers.  This form is the same workgroup — one per
+// (unit, head, block of NW*32 virtual rows), the same fragment layouts, softmax_pv_tile and output path — with the staging
+// taken out of the critical path:
+//   * two LDS buffers of LONG_NKEY = 128 keys (K [128][72] + V^T [64][136] = 35,840 B each; 71,680 B per workgroup, two
+//     workgroups per CU);
+//   * the global loads of chunk c+1 are issued as one batch into registers (2 + 2 16-byte loads per thread with 8 waves,
+//     4 + 4 with 4) BEFORE the key tiles of chunk c and written to the other buffer after them: the HBM / L2 round trip
+//     runs under the MFMAs, and one barrier per chunk orders "buffer written" before "buffer read" and "buffer read"
+//     before its next overwrite (a buffer is rewritten one full iteration — one barrier — after its last reader);
+//   * the output transposition scratch (store_rows_lds) re-uses the buffers after the last chunk's barrier.
+// An ordinary grid sized by max_rows that ends: empty row tiles return at once.
+// A row's bits depend on its Q row, the unit's K / V and its key limit alone: every form (NW = 4 / 8, any max_group, any
+// position of the row in its unit) consumes the same 32-key tiles in the same order; a tile that lies past every limit of a
+// wave is skipped, which is what the arithmetic would have produced (p = 0 for each of its keys, reference m untouched).
+constexpr int LONG_NKT = 4;
+constexpr int LONG_NKEY = LONG_NKT * 32;
+constexpr int kLongMaxNk = 16384;      // the tested range ends at 16 x 577 = 9,232 keys
+
+template <typename T, int NW>
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void attn_long_kernel(const AttnP<T> p) {
+  using f16 = T;
+  using f16x8 = typename Elt<T>::x8;
+  constexpr int NKT = LONG_NKT, NKEY = LONG_NKEY;
+  constexpr int VROW = NKEY + 8;       // (2*NKEY+16)/16 = 17, odd: conflict-free ds_read_b128 across 16 rows
+  constexpr int NT = NW * 64;
+  constexpr int BUF = NKEY * KROW * 2 + 64 * VROW * 2;   // bytes of one K + V^T buffer
+  constexpr int KIT = NKEY * 8 / NT;   // 16-byte pieces of K (and as many of V) per thread and chunk
+  static_assert(NKEY * 8 % NT == 0 && 64 * NKT * 4 == NKEY * 8, "a chunk is a whole number of pieces per thread");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hi = lane >> 5, l31 = lane & 31;
+  const int h = blockIdx.y;
+  int bk, first, count;
+  resolve_unit(p, blockIdx.z, bk, first, count);
+  const int rows = count * p.Nq;
+  const int nk = p.Nk;
+  const int base = blockIdx.x * (NW * 32);
+  if (base >= rows) return;  // uniform: this row tile is empty for this unit
+
+  const f16* kg = p.k + ((size_t)bk * p.H + h) * p.Tk_cap * 64;
+  const f16* vg = p.vt + ((size_t)bk * p.H + h) * 64 * (size_t)p.NP;          // V^T form (NP != 0)
+  const f16* vrow = p.vt + ((size_t)bk * p.H + h) * p.Tk_cap * 64;            // row-major form (NP == 0)
+  const bool vrm = p.NP == 0;
+
+  f16x8 kreg[KIT], vreg[KIT];          // the chunk in flight
+  // Every global load of chunk k0, as range-checked buffer loads over the unit's K / V (whole byte offset in the vector
+  // operand): keys / columns past the end read as zero — masked P is 0 but 0 * garbage must stay 0 — without a predicate or a
+  // 64-bit address per piece.
+  const __amdgpu_buffer_rsrc_t rk = uniform_rsrc(kg, (uint32_t)nk * 128u);
+  const __amdgpu_buffer_rsrc_t rv = vrm ? uniform_rsrc(vrow, (uint32_t)nk * 128u) : uniform_rsrc(vg, 128u * (uint32_t)p.NP);
+  auto gload = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < KIT; ++i) {
+      const int q = tid + i * NT;                       // row q >> 3, 16-byte piece q & 7
+      kreg[i] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rk, (k0 * 8 + q) * 16, 0, 0));
+    }
+    if (vrm) {
+#pragma unroll
+      for (int i = 0; i < KIT; ++i) {
+        const int q = tid + i * NT;
+        const int c = q / NKEY, r = q - c * NKEY;       // lanes walk consecutive keys of one 8-d piece
+        vreg[i] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rv, (k0 + r) * 128 + c * 16, 0, 0));
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < KIT; ++i) {
+        const int q = tid + i * NT;
+        const int d = q / (NKT * 4), kc = q - d * (NKT * 4);
+        const int pos0 = k0 + kc * 8;                   // storage columns pos0..pos0+7 (key = vt_pos(column))
+        const bool in = (pos0 & ~15) < nk && pos0 + 8 <= p.NP;
+        vreg[i] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rv, in ? (d * p.NP + pos0) * 2 : (int)0x80000000, 0, 0));
+      }
+    }
+  };
+  // ... and their LDS stores, into buffer `buf` (the staged kernel's images: K rows of KROW halfs, V^T rows of VROW)
+  auto lstore = [&](int k0, char* buf) {
+    f16* Ks = (f16*)buf;
+    f16* Vs = (f16*)(buf + NKEY * KROW * 2);
+#pragma unroll
+    for (int i = 0; i < KIT; ++i) {
+      const int q = tid + i * NT;
+      *(f16x8*)(Ks + (q >> 3) * KROW + (q & 7) * 8) = kreg[i];
+    }
+    if (vrm) {
+#pragma unroll
+      for (int i = 0; i < KIT; ++i) {
+        const int q = tid + i * NT;
+        const int c = q / NKEY, r = q - c * NKEY;
+        const int col = vt_pos(r);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) Vs[(c * 8 + e) * VROW + col] = vreg[i][e];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < KIT; ++i) {
+        const int q = tid + i * NT;
+        const int d = q / (NKT * 4), kc = q - d * (NKT * 4);
+        const int pos0 = k0 + kc * 8;
+        f16x8 v = vreg[i];
+        if ((pos0 | 15) + 1 > nk) {                     // the 16-key block that straddles Nk: zero the keys past the end
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (vt_pos(pos0 + e) >= nk) v[e] = (f16)0.f;
+        }
+        *(f16x8*)(Vs + d * VROW + kc * 8) = v;
+      }
+    }
+  };
+
+  // this wave's 32 rows: one block per wave, its (m, l, O) lives across every chunk
+  const int v0 = base + wave * 32;
+  const bool active = v0 < rows;                        // waves without rows still stage and meet the barriers
+  const RowInfo ri = row_info(p, (active ? v0 : 0) + l31, first, rows);
+  f16x8 qf[4];
+  {
+    const f16* qg = p.q + (((size_t)ri.qb * p.H + h) * p.Tq_cap + ri.t) * 64 + hi * 8;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const f16x8*)(qg + ks * 16);
+  }
+  gload(0);
+  // smallest / largest key limit in the wave: from which tile on masking is needed, and where the wave's keys end
+  int kmin = ri.klim, kmax = ri.klim;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int x = __shfl_xor(kmin, o, 64), y = __shfl_xor(kmax, o, 64);
+    kmin = x < kmin ? x : kmin;
+    kmax = y > kmax ? y : kmax;
+  }
+  float m = -INFINITY, l = 0.f;
+  f32x16 O[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) O[dt][r] = 0.f;
+
+  lstore(0, smem);
+  if (NKEY < nk) gload(NKEY);
+  __syncthreads();
+  int cur = 0;
+#pragma unroll 1
+  for (int k0 = 0; k0 < nk; k0 += NKEY) {
+    if (active) {
+      const f16* Ks = (const f16*)(smem + cur * BUF);
+      const f16* Vs = (const f16*)(smem + cur * BUF + NKEY * KROW * 2);
+#pragma unroll 1
+      for (int kt = 0; kt < NKT; ++kt) {
+        const int key0 = k0 + kt * 32;
+        if (key0 >= nk || key0 >= kmax) break;          // (kmax <= Nk; a row whose limit is 0 keeps m = -inf, l = 0, O = 0)
+        f32x16 S;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) S[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          const f16x8 kf = *(const f16x8*)(Ks + (kt * 32 + l31) * KROW + ks * 16 + hi * 8);
+          S = Elt<T>::mfma32(kf, qf[ks], S);
+        }
+        const bool need_mask = (key0 + 32) > kmin;
+        auto vfrag = [&](int dt, int hb) { return *(const f16x8*)(Vs + (dt * 32 + l31) * VROW + (kt * 2 + hb) * 16 + 8 * hi); };
+        if (need_mask) softmax_pv_tile<T, true>(S, key0, ri.klim, true, m, l, O, vfrag);
+        else softmax_pv_tile<T, false>(S, key0, ri.klim, false, m, l, O, vfrag);
+      }
+    }
+    if (k0 + NKEY < nk) {
+      lstore(k0 + NKEY, smem + (cur ^ 1) * BUF);        // (last read one iteration ago: every wave has passed a barrier since)
+      if (k0 + 2 * NKEY < nk) gload(k0 + 2 * NKEY);
+    }
+    __syncthreads();                                    // the one barrier of a chunk (after the last: the scratch below)
+    cur ^= 1;
+  }
+  if (!active) return;
+  l += __shfl_xor(l, 32, 64);
+  const float inv = l > 0.f ? 1.0f / l : 0.f;
+  if (p.ostage) store_rows_lds(p, ri, h, O, inv, smem + wave * 2048);
+  else store_rows(p, ri, h, O, inv);
 }
 
 // ------------------------------------------------------------------ streamed kernel (tower self-attention)
@@ -1171,6 +1354,22 @@ int launch_stream(const AttnP<T>& p, hipStream_t s) {
   return VIDIL_OK;
 }
 
+template <typename T, int NW>
+int launch_long(const AttnP<T>& p, int max_rows, hipStream_t s) {
+  constexpr int smem = 2 * (LONG_NKEY * KROW * 2 + 64 * (LONG_NKEY + 8) * 2);   // (attn_long_kernel: 2 x BUF)
+  static_assert(2 * smem <= 160 * 1024 && NW * 2048 <= smem, "two workgroups per CU; the output scratch fits the buffers");
+  static std::atomic<unsigned long long> attr_set{0};   // (one bit per device that has the opt-in: vidil_lds_opt_in)
+  auto kern = attn_long_kernel<T, NW>;
+  if (const int rc_ = vidil_lds_opt_in(attr_set, (const void*)kern, smem, "attention (long-key kernel)")) return rc_;
+  AttnP<T> q = p;
+  q.ostage = (p.ldo % 8 == 0 && ((uintptr_t)p.out & 15) == 0) ? 1 : 0;   // (16-byte stores)
+  q.rb = 1;
+  dim3 grid((max_rows + NW * 32 - 1) / (NW * 32), p.H, p.n_kv);
+  hipLaunchKernelGGL(kern, grid, dim3(NW * 64), smem, s, q);
+  VIDIL_CHECK_LAUNCH("attention/long");
+  return VIDIL_OK;
+}
+
 template <typename T, bool QS>
 int launch_direct1(const AttnP<T>& p, hipStream_t s) {
   VIDIL_REQUIRE((long long)p.H * p.n_kv < 0x7fffffffLL, "attention: H=%d x %d kv batches overflow the unit index", p.H, p.n_kv);
@@ -1218,6 +1417,15 @@ int attention_dispatch(const AttnP<T>& p, int nkt, int max_rows, int Nk, hipStre
     if (max_rows <= 32) return launch_direct1<T, false>(p, s);
     if (max_rows > 128) return launch_lds<T, 7, 8>(p, max_rows, s);
     return launch_lds<T, 7, 4>(p, max_rows, s);
+  }
+  // the long-key form (attn_long_kernel): more than 32 query rows per unit, plain K / V, plain 16-bit output rows
+  if (max_rows > 32 && !p.tiled && p.out_mode == 0 && Nk <= kLongMaxNk) {
+    if (p.causal) {
+      vidil_set_error("attention: causal masks are not supported by the long-key form (Nk=%d > 768)", Nk);
+      return VIDIL_EUNSUP;
+    }
+    if (max_rows > 128) return launch_long<T, 8>(p, max_rows, s);
+    return launch_long<T, 4>(p, max_rows, s);
   }
   vidil_set_error("attention: Nk=%d > 768 not supported by these kernels", Nk);
   return VIDIL_EUNSUP;

@@ -281,7 +281,11 @@ def split3(x32, out16):
 def attention(q, k, vt, out, *, Bq, H, Nq, Nk, Tq_cap, Tk_cap, NP, kv_group=1, causal=False,
               causal_off=0, kv_len=None, kv_index=None, group_start=None, max_group=0, ldo=None, kv_tiled=False,
               split3=False):
-    """group_start: int32 [n_kv+1] device prefix table (query batches per kv batch), with max_group.
+    """softmax(q k^T) v per head of 64 (vidil_attention).  Nk <= 768 keys in every form; Nk up to 16384 (a video's frames as
+    one encoder sequence) in the long-key form, which needs more than 32 query rows per unit (max_group * Nq, kv_group * Nq,
+    or Nq with kv_index), plain K / V (not kv_tiled), no causal mask and plain 16-bit output rows — anything else over 768 keys
+    raises VidilHipError("... not supported ...").  max_group is an upper bound: row tiles past a unit's rows return at once.
+    group_start: int32 [n_kv+1] device prefix table (query batches per kv batch), with max_group.
     kv_tiled: k / vt are fragment-tiled (gemm heads=dict(tiled=True)); at most 32 query rows per unit.
     split3: ``out`` is [rows, 3*H*64] and receives the error-compensated operand rows [hi | lo | hi] (VIDIL_DT_SPLIT3)."""
     lib = _lib.load()

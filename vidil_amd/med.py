@@ -481,17 +481,36 @@ class BertModel(PackedCache, nn.Module):
                 # every query batch that shares an image (the beams of a caption search, the captions of a
                 # frame) is served by one fetch of that image's K/V: see vidil_attention's grouping forms
                 K.gemm(h16, d["cq_w"], d["cq_b"], heads=dict(q=q, T=T, H=H, part0=0, Tq_cap=T, q_scale=0.125))
+                mg = self._cross_bound(cross, T, cross_index, cross_group, cross_groups, cross_max_group)
                 for b0, b1 in self._cross_blocks(cross, cross_index, cross_groups):
                     r0, r1 = (0, rows) if (b0, b1) == (0, cross.B) else (b0 * cross_group, b1 * cross_group)
                     K.attention(q[r0:r1], cross.k[i][b0:b1], cross.vt[i][b0:b1], o[r0 * T:r1 * T], Bq=r1 - r0, H=H, Nq=T, Nk=cross.Te,
                                 Tq_cap=T, Tk_cap=cross.Tk_cap, NP=cross.NP, kv_group=cross_group, kv_index=cross_index,
-                                group_start=cross_groups, max_group=cross_max_group, kv_tiled=cross.tiled, **ckl(r0, r1))
+                                group_start=cross_groups, max_group=mg, kv_tiled=cross.tiled, **ckl(r0, r1))
                 K.gemm(o, d["co_w"], d["co_b"], out=tmp, resid=h32)
                 K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=h16, out32=h32)
             K.gemm(h16, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
             K.gemm(inter, d["o_w"], d["o_b"], out=tmp, resid=h32)
             K.layernorm(tmp, d["o_g"], d["o_bt"], eps, out16=h16, out32=h32)
         return h32, h16
+
+    #: vidil_attention's short kernels end here; past it only the long-key form exists, which needs MORE than 32 query rows per unit
+    LONG_KEYS = 768
+
+    def _cross_bound(self, cross, Nq, cross_index, cross_group, cross_groups, cross_max_group):
+        """The ``max_group`` bound of a cross-attention launch.  Up to LONG_KEYS encoder states it is the caller's; over more (a
+        video's frames concatenated as one encoder sequence) every launch must present more than 32 query rows per unit, so
+        the bound of the ``group_start`` form is rounded up to ceil(33 / Nq) — it is an upper bound, row tiles past a unit's
+        last row return at once — and the other forms are refused where they cannot reach 33 rows."""
+        if cross.Te <= self.LONG_KEYS:
+            return cross_max_group
+        if cross_groups is not None:
+            return max(cross_max_group, -(-33 // Nq))
+        rows = Nq * (1 if cross_index is not None else cross_group)
+        if rows <= 32:
+            raise K.VidilHipError(f"cross-attention over {cross.Te} > {self.LONG_KEYS} encoder states needs more than 32 query rows per "
+                                  f"unit (got {rows}): order the pairs image-major and use group_start")
+        return cross_max_group
 
     @staticmethod
     def _cross_len_arg(cross_kv_len, rows):
@@ -732,11 +751,12 @@ class BertModel(PackedCache, nn.Module):
             if stop_after_self:
                 return h32, h16, stats[cur], pend
             consumer("cq", i, d["cq_w"], d["cq_b"], heads=dict(q=q, T=T, H=H, part0=0, Tq_cap=T, q_scale=0.125))
+            mg = self._cross_bound(cross, T, cross_index, cross_group, cross_groups, cross_max_group)
             for b0, b1 in self._cross_blocks(cross, cross_index, cross_groups):
                 r0, r1 = (0, rows) if (b0, b1) == (0, cross.B) else (b0 * cross_group, b1 * cross_group)
                 K.attention(q[r0:r1], cross.k[i][b0:b1], cross.vt[i][b0:b1], o[r0 * T:r1 * T], Bq=r1 - r0, H=H, Nq=T, Nk=cross.Te,
                             Tq_cap=T, Tk_cap=cross.Tk_cap, NP=cross.NP, kv_group=cross_group, kv_index=cross_index,
-                            group_start=cross_groups, max_group=cross_max_group, kv_tiled=cross.tiled, **ckl(r0, r1))
+                            group_start=cross_groups, max_group=mg, kv_tiled=cross.tiled, **ckl(r0, r1))
             residual_gemm(o, d["co_w"], d["co_b"], d["co_g"], d["co_bt"])
             consumer("fc1", i, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
             residual_gemm(inter, d["o_w"], d["o_b"], d["o_g"], d["o_bt"])
@@ -858,8 +878,10 @@ class BertModel(PackedCache, nn.Module):
         if cross is not None:
             vt, NP = (cross.vt[L - 1], cross.NP) if cross.last_vt is None else (cross.last_vt, cross.last_NP)
             K.gemm(c16, d["cq_w"], d["cq_b"], heads=dict(q=q1, T=1, H=H, part0=0, Tq_cap=1, q_scale=0.125))
+            # (over LONG_KEYS encoder states: the bound becomes max(max_group, 33) — one query row per pair)
             K.attention(q1, cross.k[L - 1], vt, o1, Bq=P, H=H, Nq=1, Nk=cross.Te, Tq_cap=1, Tk_cap=cross.Te, NP=NP,
-                        kv_index=cross_index, group_start=cross_groups, max_group=cross_max_group)
+                        kv_index=cross_index, group_start=cross_groups,
+                        max_group=self._cross_bound(cross, 1, cross_index, 1, cross_groups, cross_max_group))
             K.gemm(o1, d["co_w"], d["co_b"], out=tmp, resid=c32)
             K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=c16, out32=c32)
         inter = K.gemm(c16, d["i_w"], d["i_b"], act=K.ACT_GELU_ERF)
