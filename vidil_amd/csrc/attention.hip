@@ -1241,17 +1241,81 @@ __global__ __launch_bounds__(256, (QS || !TILED) ? 2 : 3) void attn_direct1_kern
 }
 
 // ------------------------------------------------------------------ one wave, one key tile
-// rows <= 32 and Nk <= 32 (decoder self-attention over the cached tokens): a single wave per (unit, head),
-// operands straight from memory, no LDS and no barrier.
-template <typename T>
-__global__ __launch_bounds__(64) void attn_wave_kernel(const AttnP<T> p) {
+// The output rows of attn_wave_kernel: store_rows_lds's transposition through 2 KiB of wave-private LDS (16 B per lane,
+// 64 contiguous bytes per row) for plain rows and, SPLIT, for the [hi | lo | hi] planes — the hi pass is written to planes
+// 0 and 2, a second pass carries lo.  Every value is rounded the pinned way (Elt<T>::from_f32: multiply, then convert), as
+// store_rows rounds the planes form; its plain f16 rows leave the choice of a fused multiply-convert to the compiler, element by
+// element, so f16 rows written here and there can differ in the last bit (bf16 has no fused form).
+template <typename T, bool SPLIT>
+__device__ __forceinline__ void store_rows_wave(const AttnP<T>& p, const RowInfo& ri, int h, const f32x16 (&O)[2], float inv, char* scratch) {
   using f16 = T;
+  using f16x4 = typename Elt<T>::x4;
   using f16x8 = typename Elt<T>::x8;
   const int lane = threadIdx.x & 63;
   const int hi = lane >> 5, l31 = lane & 31;
-  const int h = blockIdx.y;
+  const int pl = p.ldo / 3;
+  // element offset of this lane's row (valid rows only) — fetched below by the lanes that store that row
+  const long long own = ri.valid ? (long long)(((size_t)ri.qb * p.Nq + ri.t) * p.ldo + h * 64) : -1;
+  long long dst[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = i * 16 + (lane >> 2);
+    const int lo = __shfl((int)(own & 0xffffffffLL), r, 64), hi32 = __shfl((int)(own >> 32), r, 64);
+    dst[i] = ((long long)hi32 << 32) | (unsigned int)lo;
+  }
+#pragma unroll
+  for (int pass = 0; pass < (SPLIT ? 2 : 1); ++pass) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        f16x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float o = O[dt][rq * 4 + e] * inv;
+          const f16 oh = Elt<T>::from_f32(o);
+          v[e] = pass == 0 ? oh : Elt<T>::from_f32(o - (float)oh);
+        }
+        *(f16x4*)(scratch + l31 * 64 + ((rq ^ ((l31 >> 1) & 3)) << 4) + hi * 8) = v;
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int r = i * 16 + (lane >> 2), c = lane & 3;
+        const f16x8 v = *(const f16x8*)(scratch + r * 64 + ((c ^ ((r >> 1) & 3)) << 4));
+        if (dst[i] >= 0) {
+          f16* const og = p.out + dst[i] + dt * 32 + c * 8;
+          if (!SPLIT) {
+            *(f16x8*)og = v;
+          } else if (pass == 0) {
+            *(f16x8*)og = v;
+            *(f16x8*)(og + 2 * pl) = v;
+          } else {
+            *(f16x8*)(og + pl) = v;
+          }
+        }
+      }
+    }
+  }
+}
+
+// rows <= 32 and Nk <= 32 (decoder self-attention over the cached tokens): a single wave per (unit, head),
+// operands straight from memory, no barrier.  Four waves per workgroup take four adjacent (unit, head) pairs — adjacent
+// heads of one K/V batch — so a workgroup start is paid once per four units.  p.ostage (launch_any: output rows 16-byte
+// aligned): rows leave through store_rows_wave; otherwise through store_rows's 8-byte stores.  An e4m3 output cannot
+// arrive here (vidil_attention: fp8 rows need more than 32 query rows per unit) and is not compiled.
+template <typename T>
+__global__ __launch_bounds__(256, 5) void attn_wave_kernel(const AttnP<T> p) {
+  using f16 = T;
+  using f16x8 = typename Elt<T>::x8;
+  __shared__ __attribute__((aligned(16))) char ostage[4 * 2048];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int hi = lane >> 5, l31 = lane & 31;
+  const int u = blockIdx.x * 4 + wave;
+  if (u >= p.H * p.n_kv) return;
+  const int z = u / p.H, h = u - z * p.H;
   int bk, first, count;
-  resolve_unit(p, blockIdx.z, bk, first, count);
+  resolve_unit(p, z, bk, first, count);
   const int rows = count * p.Nq;
   if (rows <= 0) return;
   const int nk = p.Nk;
@@ -1287,7 +1351,8 @@ __global__ __launch_bounds__(64) void attn_wave_kernel(const AttnP<T> p) {
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) O[dt][r] = 0.f;
-  softmax_pv_tile<T>(S, 0, ri.klim, true, m, l, O, [&](int dt, int hb) {
+  // FIRST: the unit's only tile — nothing is accumulated yet, so there is no reference to move and nothing to rescale
+  softmax_pv_tile<T, true, true, true>(S, 0, ri.klim, true, m, l, O, [&](int dt, int hb) {
     const int blk0 = hb * 16;
     f16x8 v = vf[dt][hb];
 #pragma unroll
@@ -1296,7 +1361,11 @@ __global__ __launch_bounds__(64) void attn_wave_kernel(const AttnP<T> p) {
     return v;
   });
   l += __shfl_xor(l, 32, 64);
-  store_rows(p, ri, h, O, l > 0.f ? 1.0f / l : 0.f);
+  const float inv = l > 0.f ? 1.0f / l : 0.f;
+  __builtin_assume(p.out_mode != 1);               // (no e4m3 rows here: store_rows's fp8 path is not compiled)
+  if (!p.ostage) store_rows(p, ri, h, O, inv);     // (uniform)
+  else if (p.out_mode == 2) store_rows_wave<T, true>(p, ri, h, O, inv, ostage + wave * 2048);
+  else store_rows_wave<T, false>(p, ri, h, O, inv, ostage + wave * 2048);
 }
 
 template <typename T, int NKT, int NW>
@@ -1388,7 +1457,10 @@ int launch_any(const AttnP<T>& p, int max_rows, hipStream_t s) {
   if constexpr (NKT == 7)
     if (stream_eligible(p, max_rows)) return launch_stream<T, NKT>(p, s);
   if (max_rows <= 32 && NKT == 1 && !p.tiled) {
-    hipLaunchKernelGGL(attn_wave_kernel<T>, dim3(1, p.H, p.n_kv), dim3(64), 0, s, p);
+    VIDIL_REQUIRE((long long)p.H * p.n_kv < 0x7fffffffLL, "attention: H=%d x %d kv batches overflow the unit index", p.H, p.n_kv);
+    AttnP<T> q = p;
+    q.ostage = ((uintptr_t)p.out & 15) == 0 ? 1 : 0;   // (16-byte stores; ldo is a multiple of 8)
+    hipLaunchKernelGGL(attn_wave_kernel<T>, dim3((p.H * p.n_kv + 3) / 4), dim3(256), 0, s, q);
     VIDIL_CHECK_LAUNCH("attention/wave");
     return VIDIL_OK;
   }
