@@ -20,6 +20,13 @@ encoder states of the answer decoder.
 
 Plain f16 / bf16 operands only: the parity precision mode and fp8 are refused.  So are more than 768 image tokens per image
 (what the attention kernels serve): the reference's default image_size=480 constructs and loads, its forward pass raises; use 384.
+
+``BLIP_Video_VQA`` / ``blip_vqa_video()`` (models/blip_vqa.py:169-346) answer questions about a VIDEO: the ViT tokens of its N
+frames are one encoder sequence of N*T keys (``video_embeds.view(B, -1, C)``, :201) — 8 x 197 = 1,576 at 224^2 —, at most
+MAX_VIDEO_TOKENS, through the long-key form of ``vidil_attention``.  Its text encoder runs image-major (``group_start``): the
+questions are sorted by video, a video's cross-attention K / V are projected once whatever the number of its questions, and
+one staging of them serves every question of the video (``question_states_grouped``).  Everything behind the
+question states — ``rank_answer``, ``generate_answer_ids``, ``answer_loss`` — is BLIP_VQA's.
 """
 from __future__ import annotations
 
@@ -27,15 +34,17 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .blip import BLIP_Decoder, create_vit, load_checkpoint, resolve_med_config
+from .blip import CLIP_MEAN, CLIP_STD, BLIP_Decoder, create_vit, load_checkpoint, resolve_med_config
 from .med import BertConfig, BertLMHeadModel, BertModel
 from .packing import FP8, compute_dtype, fp8_companion, parity_mode, require_cuda, set_compute_dtype, set_parity_mode
 from .tokenizer import init_tokenizer, refuse_synthetic_with_checkpoint
+from .video_retrieval import default_videos_per_block, phase_timer
 
 VQA_QUESTION_MAX_LENGTH = 35     # models/blip_vqa.py:42
 VQA_NUM_BEAMS, VQA_MAX_LENGTH, VQA_MIN_LENGTH = 3, 10, 1    # models/blip_vqa.py:92,100-102
 VQA_LABEL_SMOOTHING = 0.1        # models/med.py:916 (the loss `rank_answer` negates)
 MAX_IMAGE_TOKENS = 768           # keys the attention kernels serve (vidil_attention: Nk <= 768): ViT-B/16 up to 432 px
+MAX_VIDEO_TOKENS = 16384         # keys of the long-key form (vidil_attention: Nk <= 16384): a video's N frames x T tokens
 
 
 class BLIP_VQA(nn.Module):
@@ -208,6 +217,170 @@ class BLIP_VQA(nn.Module):
 def blip_vqa(pretrained="", **kwargs):
     """Reference: models/blip_vqa.py:334-339 (does not assert on the missing keys)."""
     model = BLIP_VQA(**kwargs)
+    if pretrained:
+        refuse_synthetic_with_checkpoint(model.tokenizer, pretrained)
+        model, msg = load_checkpoint(model, pretrained)
+    return model
+
+
+# ====================================================================================================== video
+def video_major_order(video_of_question, n_videos):
+    """The video-major order of questions that arrive in any order (host index tensors; pure).
+
+    video_of_question int [Q]: the video every question asks about.  Returns a dict: ``order`` int64 [Q] — the caller's index of
+    the question at every sorted position (stable: a video's questions keep the caller's order); ``inverse`` int64 [Q] — the
+    sorted position of every caller's question (``sorted[inverse]`` is the caller's order again); ``group_start`` int32
+    [n_videos+1] — the sorted questions of video v are group_start[v] .. group_start[v+1]-1 (empty for a video nobody asks
+    about); ``max_group`` — its largest gap."""
+    v = torch.as_tensor(video_of_question).cpu().long().view(-1)
+    if v.numel() and not (0 <= int(v.min()) and int(v.max()) < n_videos):
+        raise ValueError(f"video_of_question must hold indices in [0, {n_videos})")
+    order = torch.argsort(v, stable=True)
+    inverse = torch.empty_like(order)
+    inverse[order] = torch.arange(v.numel())
+    group_start = torch.zeros(n_videos + 1, dtype=torch.int64)
+    group_start[1:] = torch.cumsum(torch.bincount(v, minlength=n_videos), 0)
+    gaps = group_start[1:] - group_start[:-1]
+    return dict(order=order, inverse=inverse, group_start=group_start.to(torch.int32),
+                max_group=int(gaps.max()) if n_videos else 0)
+
+
+class BLIP_Video_VQA(BLIP_VQA):
+    """models/blip_vqa.py:169-331: BLIP_VQA over ``video_representation: concat_frame``.  Same members and parameter names, so
+    a BLIP_VQA checkpoint loads as it does there."""
+
+    def _require_video_tokens(self, n_tokens):
+        """A video's frames are ONE encoder sequence for the text encoder's cross-attention, and the long-key form of the
+        attention kernels serves at most MAX_VIDEO_TOKENS keys: refuse more here, by name, before anything is launched."""
+        if n_tokens > MAX_VIDEO_TOKENS:
+            raise ValueError(f"BLIP_Video_VQA: {n_tokens} tokens per video (frames x tokens per frame) exceed the {MAX_VIDEO_TOKENS} "
+                             f"keys the attention kernels serve — sample fewer frames or build the model with a smaller image_size")
+
+    # ------------------------------------------------------------------ frames -> tokens
+    @torch.no_grad()
+    def video_tokens(self, video):
+        """f32 [B,N,3,S,S] (normalised) -> 16-bit [B*N*T, width]: the ViT over the B*N frames.  A video's N*T rows are
+        contiguous — as encoder states it is ONE unit of N*T tokens (models/blip_vqa.py:198-201), no copy."""
+        if video.dim() != 5 or video.shape[2] != 3:
+            raise ValueError(f"BLIP_Video_VQA: f32 [B,N,3,S,S] expected, got {tuple(video.shape)}")
+        B, N = video.shape[:2]
+        self._require_image_tokens()
+        self._require_video_tokens(N * (self.visual_encoder.patch_embed.num_patches + 1))
+        require_cuda(video, "BLIP_Video_VQA.video_tokens")
+        self._require_plain()
+        return self.visual_encoder.forward_both(video.reshape(B * N, *video.shape[2:]))[1]
+
+    @torch.no_grad()
+    def video_tokens_u8(self, frames_u8):
+        """uint8 [B,N,S,S,3] frames (already S x S) -> the same, with /255 and the normalisation fused into the patch kernel
+        (BLIP_Retrieval.video_features_u8's preprocessing)."""
+        if frames_u8.dim() != 5 or frames_u8.shape[-1] != 3 or frames_u8.dtype != torch.uint8:
+            raise ValueError(f"BLIP_Video_VQA: uint8 [B,N,S,S,3] expected, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+        B, N = frames_u8.shape[:2]
+        self._require_image_tokens()
+        self._require_video_tokens(N * (self.visual_encoder.patch_embed.num_patches + 1))
+        require_cuda(frames_u8, "BLIP_Video_VQA.video_tokens_u8")
+        self._require_plain()
+        return self.visual_encoder.forward_u8(frames_u8.reshape(B * N, *frames_u8.shape[2:]), CLIP_MEAN, CLIP_STD)[1]
+
+    # ------------------------------------------------------------------ question states, a video shared by its questions
+    @torch.no_grad()
+    def question_states_grouped(self, tokens16, B, ids, lens, video_of_question, videos_per_block=None, timings=None, f32=True):
+        """models/blip_vqa.py:217-221,248-252 for Q questions about B videos, in ANY order.  tokens16 16-bit [B*Te, width] (Te =
+        N*T tokens per video, or T of one frame); ids i32 [Q, Tq] / lens i32 [Q] (``tokenize_questions``); video_of_question
+        int [Q].  Returns (h32, h16) [Q*Tq, C] in the caller's order: every position's last hidden state (pad positions too).
+
+        The questions are sorted video-major (``video_major_order``) and the videos walked in blocks of ``videos_per_block``
+        (default: what fits video_retrieval.KV_BLOCK_BYTES): a block's cross-attention K / V are projected ONCE per video and
+        the text encoder runs over the block's questions with the ``group_start`` table, so one staging of a video's K / V
+        serves all its questions; a video without a question is an empty group.  Every block is launched with the same Tq
+        (ids' width: the longest question of the call) and the same ``max_group`` bound — the largest group of the call,
+        rounded up to more than 32 query rows per video, which the kernels past 768 keys need and which keeps one kernel
+        family (row-major values) at every group size: row tiles past a video's last question return at once.  A question's
+        bits therefore do not depend on the block size.
+        ``f32=False``: the f32 copy of the states is not assembled and None is returned in its place (the answer decoder reads
+        the 16-bit rows only).  The blocks' rows are joined by one copy (none when the call is one block) and put into the
+        caller's order by one ``index_select`` (none when the questions arrive video-major).
+        ``timings`` (dict, optional): receives the seconds spent in ``kv`` / ``encoder`` (video_retrieval.phase_timer)."""
+        require_cuda(tokens16, "BLIP_Video_VQA")
+        self._require_plain()
+        if B <= 0 or tokens16.shape[0] % B:
+            raise ValueError(f"BLIP_Video_VQA: {tokens16.shape[0]} token rows do not divide into B={B} videos")
+        Te = tokens16.shape[0] // B
+        self._require_video_tokens(Te)
+        Q, Tq = ids.shape
+        sched = video_major_order(video_of_question, B)
+        if sched["order"].numel() != Q or lens.numel() != Q:
+            raise ValueError(f"BLIP_Video_VQA: {Q} questions, {lens.numel()} lengths and {sched['order'].numel()} entries of "
+                             f"video_of_question")
+        te, dev = self.text_encoder, tokens16.device
+        C = te.config.hidden_size
+        order, gs = sched["order"], sched["group_start"].long()
+        max_group = max(sched["max_group"], -(-33 // Tq))
+        ids_s = ids.cpu()[order].to(torch.int32).to(dev).contiguous()
+        lens_s = lens.cpu()[order].to(torch.int32).to(dev).contiguous()
+        parts32, parts16 = [], []
+        if videos_per_block is None:
+            videos_per_block = default_videos_per_block(self, Te)
+        if videos_per_block < 1:
+            raise ValueError(f"BLIP_Video_VQA: videos_per_block={videos_per_block}")
+        lap = phase_timer(timings)
+        for b0 in range(0, B, videos_per_block):
+            b1 = min(B, b0 + videos_per_block)
+            p0, p1 = int(gs[b0]), int(gs[b1])
+            if p1 == p0:
+                continue
+            t0 = lap()
+            cross = te.project_cross_kv(tokens16[b0 * Te:b1 * Te], b1 - b0, Te, v_rowmajor=True)
+            t0 = lap("kv", t0)
+            a32, a16 = te.encode(ids_s[p0:p1], lens_s[p0:p1], cross,
+                                 cross_groups=(gs[b0:b1 + 1] - p0).to(torch.int32).to(dev).contiguous(), cross_max_group=max_group)
+            if f32:
+                parts32.append(a32)
+            parts16.append(a16)
+            lap("encoder", t0)
+        back = None if torch.equal(order, torch.arange(Q)) else sched["inverse"].to(dev)
+
+        def joined(parts):                   # (blocks are in sorted order and every question belongs to one of them)
+            h = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+            return h if back is None else h.view(Q, Tq, C).index_select(0, back).view(Q * Tq, C)
+
+        return (joined(parts32) if f32 else None), joined(parts16)
+
+    # ------------------------------------------------------------------ the reference's call
+    def _answer(self, states16, Q, lens, answer, n, weights, train, inference, k_test):
+        """What BLIP_VQA.forward does behind the question states (models/blip_vqa.py:208-280)."""
+        if train:
+            a_ids, a_lens = self.tokenize_answers(answer)
+            loss = self.answer_loss(states16, Q, lens, a_ids, a_lens, n)
+            w = torch.as_tensor(weights, dtype=torch.float32).to(loss.device).view(-1)
+            return ((w.double() * loss.double()).sum() / Q).float()
+        if inference == "generate":
+            out_tok, _ = self.generate_answer_ids(states16, Q)
+            return [self.tokenizer.decode(row, skip_special_tokens=True) for row in out_tok.cpu().tolist()]
+        a_ids, a_lens = self.tokenize_answers(answer)
+        return self.rank_answer(states16, Q, lens, a_ids, a_lens, k_test)[0]
+
+    @torch.no_grad()
+    def forward(self, video, question, answer=None, n=None, weights=None, train=True, inference="rank", k_test=128):
+        """Reference: models/blip_vqa.py:196-280.  video f32 [B,N,3,S,S] on the GPU, one question per video.
+        train=True: the 0-dim f32 loss (weights * per-answer loss).sum() / B, no backward pass; train=False, 'generate':
+        list[str]; train=False, 'rank': int64 [B] indices into the answer list, on the GPU.  The case video_of_question =
+        arange(B) of ``question_states_grouped``."""
+        if not train and inference not in ("generate", "rank"):
+            raise ValueError(f"unknown inference {inference!r} (generate | rank)")
+        B = video.shape[0]
+        ids, lens = self.tokenize_questions(question)
+        if ids.shape[0] != B:
+            raise ValueError(f"BLIP_Video_VQA: {ids.shape[0]} questions for {B} videos")
+        tokens = self.video_tokens(video)
+        _, states16 = self.question_states_grouped(tokens, B, ids, lens, torch.arange(B))
+        return self._answer(states16, B, lens, answer, n, weights, train, inference, k_test)
+
+
+def blip_vqa_video(pretrained="", **kwargs):
+    """Reference: models/blip_vqa.py:341-346 (does not assert on the missing keys)."""
+    model = BLIP_Video_VQA(**kwargs)
     if pretrained:
         refuse_synthetic_with_checkpoint(model.tokenizer, pretrained)
         model, msg = load_checkpoint(model, pretrained)

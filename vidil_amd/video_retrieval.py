@@ -28,6 +28,7 @@ from __future__ import annotations
 
 import json
 import re
+import time
 
 import numpy as np
 import torch
@@ -104,6 +105,22 @@ def default_videos_per_block(model, tokens_per_video):
     cfg = model.text_encoder.config
     per_video = cfg.num_hidden_layers * 2 * tokens_per_video * cfg.hidden_size * 2
     return max(1, KV_BLOCK_BYTES // per_video)
+
+
+def phase_timer(timings):
+    """lap = phase_timer(timings): ``t0 = lap()`` marks a start on the current stream and ``lap(name, t0)`` adds the seconds
+    between that mark and now to timings[name] (HIP events, synchronised at the end of the phase) and returns a new mark.
+    With ``timings`` None nothing is recorded and nothing is synchronised."""
+    def lap(name=None, t0=None):
+        if timings is None:
+            return None
+        now = torch.cuda.Event(enable_timing=True)
+        now.record()
+        if name is not None:
+            now.synchronize()
+            timings[name] = timings.get(name, 0.0) + t0.elapsed_time(now) / 1e3
+        return now
+    return lap
 
 
 # ---------------------------------------------------------------------------------------------- evaluation
