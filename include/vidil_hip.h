@@ -202,7 +202,7 @@ int vidil_layernorm(const float* x, int64_t x_stride, const float* gamma,
 /* with more than 32 query rows per unit (max_group*Nq, kv_group*Nq, or Nq     */
 /* with kv_index), kv_tiled == 0, causal == 0 and out_dtype == dtype, with      */
 /* row-major V or V^T, all three unit forms and kv_len; every other launch over */
-/* 768 keys returns VIDIL_EUNSUP.  max_group is an upper bound: row tiles past  */
+/* 768 keys (but kv_tiled == 2, below) returns VIDIL_EUNSUP.  max_group is an upper bound: row tiles past  */
 /* a unit's last row return at once.  A row's bits there depend on its Q row,   */
 /* the unit's K / V and its key limit alone, not on the launch around it.       */
 /* Q  T16 [Bq][H][Tq_cap][64] (already scaled by 1/sqrt(64)),                 */
@@ -221,6 +221,16 @@ int vidil_layernorm(const float* x, int64_t x_stride, const float* gamma,
 /* [Bk][H][Tk_cap/32][2048], NP ignored, Tk_cap % 32 == 0) — allowed when every */
 /* work unit has at most 32 query rows (the cross-attention of the caption      */
 /* decoder, which re-reads the image K/V from HBM on every decode step).        */
+/* kv_tiled is a selector: 0 = plain rows; 1 = fragment tiles, Nk <= 768 (more  */
+/* keys return VIDIL_EUNSUP); 2 = fragment tiles, KEY-SPLIT form allowed: up to */
+/* 768 keys dispatched exactly as 1 (same kernels, same bits); 768 < Nk <=      */
+/* 16384 (the beams of a caption search over a video's concatenated frame       */
+/* tokens) on attn_dsplit_kernel — one workgroup per (kv batch, head), the key  */
+/* tiles cut into one contiguous slice per wave, the partials merged once in    */
+/* LDS in fixed wave order; all three unit forms and kv_len, out_dtype == dtype */
+/* or dtype | VIDIL_DT_SPLIT3; causal != 0 and Nk > 16384 return VIDIL_EUNSUP.  */
+/* A row's bits there depend on its Q row, the unit's K / V and its key limit   */
+/* alone; a row with no key (kv_len == 0) is zeros.                             */
 /* Which key/value batch a query batch b reads — three forms, all of which let */
 /* every query that shares a K/V (the captions of a frame, the beams of an     */
 /* image) be served by ONE staging of that K/V:                               */

@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from . import kernels as K
 from .med import BeamArena, BertConfig, BertLMHeadModel, CrossKV
-from .packing import require_cuda
+from .packing import FP8, compute_dtype, parity_mode, require_cuda
 from .tokenizer import init_tokenizer, refuse_synthetic_with_checkpoint  # noqa: F401  (init_tokenizer re-exported, reference API)
 from .vit import VisionTransformer, interpolate_pos_embed
 
@@ -26,6 +26,8 @@ _DEFAULT_MED_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)   # run_video_CapFilt.py:133
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 CAPTION_MAX_LENGTH = 40                           # models/blip.py:109 (captions given to forward are cut to 40 tokens)
+MAX_VIDEO_TOKENS = 16384                          # keys of vidil_attention's long-key and key-split forms: N frames x T tokens
+VIT_VIDEOS = 16                                   # videos per ViT pass of BLIP_Video_Decoder (video_qa.VIT_VIDEOS)
 
 
 def resolve_med_config(path):
@@ -581,6 +583,168 @@ class BLIP_Decoder(nn.Module):
 def blip_decoder(pretrained="", **kwargs):
     """Reference: models/blip.py:269-274."""
     model = BLIP_Decoder(**kwargs)
+    if pretrained:
+        refuse_synthetic_with_checkpoint(model.tokenizer, pretrained)
+        model, msg = load_checkpoint(model, pretrained)
+        assert len(msg.missing_keys) == 0
+    return model
+
+
+class BLIP_Video_Decoder(BLIP_Decoder):
+    """models/blip.py:169-266: the captioner over ``video_representation: concat_frame``.  Same members, parameter names and
+    checkpoint as BLIP_Decoder; the ViT runs over the B*N frames and a video's N*T token rows, contiguous as the ViT leaves
+    them, are ONE encoder sequence for the decoder's cross-attention (:199-200, 224-225) — no copy.
+
+    A search presents num_beams rows per video on every decode step (4 on the shared prompt pass) over those N*T keys: the
+    DecoderSession keeps the video's K / V in fragment tiles and its cross-attention launches take the key-split form of
+    ``vidil_attention`` (kv_tiled = 2) past BertModel.LONG_KEYS keys; up to that many keys (short clips, small
+    frames) they are the launches of BLIP_Decoder.  The teacher-forced loss (``forward`` / ``caption_nll``) has more than 32
+    rows per video in every launch and runs on the long-key form, as the video-level retrieval and QA heads do."""
+
+    #: read by packing.set_parity_mode / set_compute_dtype: why this model refuses the parity precision mode and fp8
+    plain_only = ("video captioning is built for plain f16 / bf16 operands (the attention forms past 768 keys have no "
+                  "error-compensated form)")
+
+    def __init__(self, med_config="configs/med_config.json", image_size=384, vit="base", vit_grad_ckpt=False,
+                 vit_ckpt_layer=0, prompt="a video of ", tokenizer=None):
+        super().__init__(med_config=med_config, image_size=image_size, vit=vit, vit_grad_ckpt=vit_grad_ckpt,
+                         vit_ckpt_layer=vit_ckpt_layer, prompt=prompt, tokenizer=tokenizer)
+
+    # ------------------------------------------------------------------ refusals, by name, before anything is launched
+    def _require_plain(self):
+        for m in self.modules():
+            if parity_mode(m):
+                raise ValueError("BLIP_Video_Decoder: the parity precision mode is not built for video captioning (the attention "
+                                 "forms past 768 keys have no error-compensated form) — set_parity_mode(False, model)")
+            if compute_dtype(m) == FP8:
+                raise ValueError("BLIP_Video_Decoder: fp8 is not built for video captioning — set_compute_dtype('f16' or 'bf16', model)")
+
+    def _require_video_tokens(self, n_tokens):
+        if n_tokens > MAX_VIDEO_TOKENS:
+            raise ValueError(f"BLIP_Video_Decoder: {n_tokens} tokens per video (frames x tokens per frame) exceed the {MAX_VIDEO_TOKENS} "
+                             f"keys the attention kernels serve — sample fewer frames or build the model with a smaller image_size")
+
+    # ------------------------------------------------------------------ frames -> tokens
+    @torch.no_grad()
+    def video_tokens(self, video):
+        """f32 [B,N,3,S,S] (normalised) -> 16-bit [B*N*T, width]: the ViT over the B*N frames, VIT_VIDEOS videos per pass; a video's
+        N*T rows are contiguous."""
+        if video.dim() != 5 or video.shape[2] != 3:
+            raise ValueError(f"BLIP_Video_Decoder: f32 [B,N,3,S,S] expected, got {tuple(video.shape)}")
+        B, N = video.shape[:2]
+        self._require_video_tokens(N * (self.visual_encoder.patch_embed.num_patches + 1))
+        self._require_plain()
+        require_cuda(video, "BLIP_Video_Decoder.video_tokens")
+        parts = [self.visual_encoder.forward_both(video[b0:b0 + VIT_VIDEOS].reshape(-1, *video.shape[2:]))[1]
+                 for b0 in range(0, B, VIT_VIDEOS)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
+    @torch.no_grad()
+    def video_tokens_u8(self, frames_u8):
+        """uint8 [B,N,S,S,3] frames (already S x S) -> the same, with /255 and the normalisation fused into the patch kernel
+        (BLIP_Video_VQA.video_tokens_u8's preprocessing)."""
+        if frames_u8.dim() != 5 or frames_u8.shape[-1] != 3 or frames_u8.dtype != torch.uint8:
+            raise ValueError(f"BLIP_Video_Decoder: uint8 [B,N,S,S,3] expected, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+        B, N = frames_u8.shape[:2]
+        self._require_video_tokens(N * (self.visual_encoder.patch_embed.num_patches + 1))
+        self._require_plain()
+        require_cuda(frames_u8, "BLIP_Video_Decoder.video_tokens_u8")
+        parts = [self.visual_encoder.forward_u8(frames_u8[b0:b0 + VIT_VIDEOS].reshape(-1, *frames_u8.shape[2:]), CLIP_MEAN, CLIP_STD)[1]
+                 for b0 in range(0, B, VIT_VIDEOS)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
+    def _tokens(self, video):
+        """(16-bit tokens [B*Te, width], B) of f32 [B,N,3,S,S] / uint8 [B,N,S,S,3] frames, or of token rows [B, Te, width]."""
+        if video.dim() == 3:
+            require_cuda(video, "BLIP_Video_Decoder")
+            return video.reshape(-1, video.shape[-1]), video.shape[0]
+        tok = self.video_tokens_u8(video) if video.dtype == torch.uint8 else self.video_tokens(video)
+        return tok, video.shape[0]
+
+    # ------------------------------------------------------------------ searches over N*T keys per video
+    def videos_per_block(self, tokens_per_video):
+        """Videos searched side by side by ``generate``: what video_retrieval.KV_BLOCK_BYTES holds of cross K / V (layers x 2 x
+        N*T x width x 2 bytes per video), at least 1 — video_retrieval.default_videos_per_block for this model's decoder."""
+        from .video_retrieval import KV_BLOCK_BYTES
+        cfg = self.text_decoder.config
+        return max(1, KV_BLOCK_BYTES // (cfg.num_hidden_layers * 2 * tokens_per_video * cfg.hidden_size * 2))
+
+    def _check_tokens(self, enc16, B):
+        self._require_plain()
+        if B <= 0 or enc16.shape[0] % B:
+            raise ValueError(f"BLIP_Video_Decoder: {enc16.shape[0]} token rows do not divide into B={B} videos")
+        self._require_video_tokens(enc16.shape[0] // B)
+
+    @torch.no_grad()
+    def generate_ids(self, enc16, B, **kw):
+        """BLIP_Decoder.generate_ids over B videos of enc16.shape[0] / B tokens each (at most MAX_VIDEO_TOKENS)."""
+        self._check_tokens(enc16, B)
+        return super().generate_ids(enc16, B, **kw)
+
+    @torch.no_grad()
+    def sample_ids(self, enc16, B, **kw):
+        self._check_tokens(enc16, B)
+        return super().sample_ids(enc16, B, **kw)
+
+    @torch.no_grad()
+    def generate(self, video, sample=False, num_beams=3, max_length=30, min_length=10, top_p=0.9, repetition_penalty=1.0,
+                 videos_per_block=None, details=None, seed=None):
+        """Reference: models/blip.py:221-266.  video f32 [B,N,3,S,S] (normalised) or uint8 [B,N,S,S,3] on the GPU -> list of B
+        captions.  As there, ``sample=True`` draws with repetition penalty 1.1 whatever ``repetition_penalty`` says (:249).
+        The videos are searched ``videos_per_block`` at a time (default: ``self.videos_per_block``); a search is per video
+        and every kernel's arithmetic is independent of the batch around a row, so a caption does not depend on the block it
+        falls in (``sample=True``: one ``seed`` for the call — default: a fresh one, as sample_ids draws it — and the video's
+        index in the call as its Philox row).  ``details`` (dict, optional; what the tests compare): receives ``tokens`` i32
+        [B, max_length] on the host."""
+        tok16, B = self._tokens(video)
+        if sample and seed is None:
+            self._sample_calls = getattr(self, "_sample_calls", 0) + 1
+            seed = (torch.initial_seed() + (self._sample_calls << 32)) & 0xFFFFFFFFFFFFFFFF
+        Te = tok16.shape[0] // B
+        per = self.videos_per_block(Te) if videos_per_block is None else int(videos_per_block)
+        if per < 1:
+            raise ValueError(f"BLIP_Video_Decoder: videos_per_block={videos_per_block}")
+        parts = []
+        for b0 in range(0, B, per):
+            b1 = min(B, b0 + per)
+            blk = tok16[b0 * Te:b1 * Te]
+            if sample:
+                parts.append(self.sample_ids(blk, b1 - b0, top_p=top_p, max_length=max_length, min_length=min_length, seed=seed,
+                                             row_offset=b0))
+            else:
+                parts.append(self.generate_ids(blk, b1 - b0, num_beams=num_beams, max_length=max_length, min_length=min_length,
+                                               repetition_penalty=repetition_penalty)[0].clone())
+        out_tok = parts[0] if len(parts) == 1 else torch.cat(parts)
+        if details is not None:
+            details["tokens"] = out_tok.cpu()
+        return self.decode_captions(out_tok)
+
+    # ------------------------------------------------------------------ scoring given captions
+    @torch.no_grad()
+    def caption_nll(self, video_or_tokens, captions, video_index=None, *, group_start=None, add_prompt=False,
+                    label_smoothing=0.1, reduction="none"):
+        """BLIP_Decoder.caption_nll for videos: f32 [B,N,3,S,S] / uint8 [B,N,S,S,3] frames (the ViT runs once per frame) or their
+        token rows [B, N*T, width].  Caption p describes video ``video_index[p]`` (default: video p), or video j owns captions
+        group_start[j] .. group_start[j+1]-1.  Every launch of the teacher-forced pass has more than 32 query rows per video."""
+        x = video_or_tokens
+        if x.dim() not in (3, 5):
+            raise ValueError(f"BLIP_Video_Decoder.caption_nll: videos [B,N,3,S,S] / [B,N,S,S,3] or video tokens [B,N*T,width] "
+                             f"expected, got {tuple(x.shape)}")
+        tok16, B = self._tokens(x)
+        self._check_tokens(tok16, B)
+        return super().caption_nll(tok16.view(B, -1, tok16.shape[-1]), captions, video_index, group_start=group_start,
+                                   add_prompt=add_prompt, label_smoothing=label_smoothing, reduction=reduction)
+
+    @torch.no_grad()
+    def forward(self, video, caption):
+        """Reference: models/blip.py:196-219 — the label-smoothed (0.1) language-model loss of the given captions, one per video,
+        averaged over their target tokens.  Returns a 0-dim f32 tensor on the device (no backward pass)."""
+        return self.caption_nll(video, caption, label_smoothing=0.1, reduction="mean")
+
+
+def blip_decoder_video(pretrained="", **kwargs):
+    """Reference: models/blip.py:276-281."""
+    model = BLIP_Video_Decoder(**kwargs)
     if pretrained:
         refuse_synthetic_with_checkpoint(model.tokenizer, pretrained)
         model, msg = load_checkpoint(model, pretrained)

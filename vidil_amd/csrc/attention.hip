@@ -2,7 +2,8 @@
 // (ViT 197 keys, CLIP 50/77/257, MED text 1..35 queries over <=20 cached or 197
 // image keys; Nk <= 768), and for the long encoder sequences of the video-level
 // heads (N frames x 197 / 577 tokens as ONE sequence, 768 < Nk <= 16384:
-// attn_long_kernel, more than 32 query rows per unit).
+// attn_long_kernel, more than 32 query rows per unit; attn_dsplit_kernel, at
+// most 32 on fragment tiles — the beams of a caption search over a video).
 //
 // Work unit = (key/value batch j, head h): all query batches that read j's K/V
 // (uniform groups of `kv_group` consecutive query batches, or an explicit prefix
@@ -1240,6 +1241,177 @@ __global__ __launch_bounds__(256, (QS || !TILED) ? 2 : 3) void attn_direct1_kern
   store_rows(p, ri, h, O, l > 0.f ? 1.0f / l : 0.f);
 }
 
+// ------------------------------------------------------------------ key-split direct kernel (decode over a video's keys)
+// rows <= 32 over 768 < Nk <= 16384 keys in fragment tiles (kv_tiled = 2: the beams of a caption search attending to a video's
+// N x T frame tokens).  attn_direct1_kernel's single wave per unit would walk 25 .. 512 tiles alone, and a search over a few
+// videos would leave most of the device idle; here a workgroup of NW waves owns the unit: its ceil(Nk / 32) key tiles are cut into
+// NW contiguous slices (wave w: tiles [w * n / NW, (w + 1) * n / NW), balanced to +-1), and every wave runs attn_direct1_kernel's
+// walk over its slice for all rows of the unit — fragments straight from HBM into MFMA operands (one contiguous KiB per wave
+// load), one tile ahead in a register ring, the exact running maximum in straight-line code, tiles past Nk never fetched.  The NW
+// partials (m, l, O 32 x 64 f32: 8.5 KiB per wave as laid out below) meet ONCE in LDS and are merged in fixed wave order 0 .. NW-1,
+// every wave merging and storing 32 / NW of the 32 accumulator registers; the rows leave with store_rows's rounding, plain or as
+// [hi | lo | hi] planes.  No workspace, no atomics: a row's bits are a function of its Q row, the unit's K / V and its key limit
+// (a lane's arithmetic involves no other row, the slices depend on Nk alone, the merge order is fixed).
+// A slice whose every key is masked for a row leaves (m, l, O) = (-inf, 0, 0) and merges with weight 2^(-inf) = 0; a row with no
+// key at all (kv_len == 0) is written as zeros.
+template <typename T, int NW>
+__global__ __launch_bounds__(NW * 64, 3) void attn_dsplit_kernel(const AttnP<T> p) {
+  using f16 = T;
+  using f16x4 = typename Elt<T>::x4;
+  using f16x8 = typename Elt<T>::x8;
+  constexpr int QW = 8 / NW;                  // register quads (4 contiguous d of a row) merged and stored per wave
+  static_assert(NW == 4 || NW == 8, "the 8 quads of a lane are dealt to 4 or 8 waves");      // (launched with NW = 4: launch_dsplit)
+  // per wave: 8 quads x 64 lanes x 16 B of O (a lane's quad is one 16-byte access), then m and l of the 64 lanes
+  constexpr int PART = 8 * 64 * 16 + 2 * 64 * 4;
+  extern __shared__ __attribute__((aligned(16))) char dsplit_smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int hi = lane >> 5, l31 = lane & 31;
+  const int z = blockIdx.x / p.H, h = blockIdx.x - z * p.H;    // (adjacent workgroups: adjacent heads of one kv batch)
+  int bk, first, count;
+  resolve_unit(p, z, bk, first, count);
+  const int rows = count * p.Nq;
+  if (rows <= 0) return;  // a kv batch nobody attends to (uniform over the workgroup: no barrier is skipped by a part of it)
+  const int nk = p.Nk;
+  const RowInfo ri = row_info(p, l31, first, rows);
+  const f16* kg = p.k + ((size_t)bk * p.H + h) * p.Tk_cap * 64;
+  const f16* vg = p.vt + ((size_t)bk * p.H + h) * 64 * (size_t)p.Tk_cap;
+  const int ntiles = (nk + 31) >> 5;
+  const int t0 = (int)(((long long)wave * ntiles) / NW), t1 = (int)(((long long)(wave + 1) * ntiles) / NW);
+
+  f16x8 kf[2][4], vf[2][2][2];
+  auto load = [&](f16x8 (&kfb)[4], f16x8 (&vfb)[2][2], int kt) {
+    // a whole tile, unconditionally: 8 loads of one contiguous KiB each from a uniform base.  The last tile's positions past Nk
+    // exist (Tk_cap is a multiple of 32) and may hold anything: a key's K row only reaches that key's scores, which the mask
+    // replaces, and its V entries are zeroed in the tile (`tail` below) — so nothing is predicated per lane here
+    const f16* kt_base = kg + (size_t)kt * 2048 + lane * 8;
+    const f16* vt_base = vg + (size_t)kt * 2048 + lane * 8;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) kfb[ks] = *(const f16x8*)(kt_base + ks * 512);
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) vfb[dt][hb] = *(const f16x8*)(vt_base + (hb * 2 + dt) * 512);
+  };
+  load(kf[0], vf[0], t0);                      // (Nk > 768 is 25 tiles or more: every slice holds at least 3)
+
+  f16x8 qf[4];
+  const f16* qg = p.q + (((size_t)ri.qb * p.H + h) * p.Tq_cap + ri.t) * 64 + hi * 8;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const f16x8*)(qg + ks * 16);
+  int kmin = ri.klim;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int x = __shfl_xor(kmin, o, 64);
+    kmin = x < kmin ? x : kmin;
+  }
+  float m = -INFINITY, l = 0.f;
+  f32x16 O[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) O[dt][r] = 0.f;
+
+  auto compute = [&](const f16x8 (&kfb)[4], const f16x8 (&vfb)[2][2], int kt) {
+    f32x16 S;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) S[r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) S = Elt<T>::mfma32(kfb[ks], qf[ks], S);
+    const bool tail = (kt * 32 + 32) > nk;  // tile reaches past the last key: V^T needs zeroing too
+    const bool need_mask = (kt * 32 + 32) > kmin;
+    auto vfrag = [&](int dt, int hb) {
+      const int blk0 = (kt * 2 + hb) * 16;
+      f16x8 v = vfb[dt][hb];
+      if (tail) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (blk0 + 4 * hi + (e & 3) + 8 * (e >> 2) >= nk) v[e] = (f16)0.f;
+      }
+      return v;
+    };
+    softmax_pv_tile<T, true, false>(S, kt * 32, ri.klim, need_mask, m, l, O, vfrag);
+  };
+#pragma unroll 1
+  for (int kt0 = t0; kt0 < t1; kt0 += 2) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int kt = kt0 + j;
+      if (kt < t1) {                               // (wave-uniform)
+        if (kt + 1 < t1) load(kf[j ^ 1], vf[j ^ 1], kt + 1);
+        compute(kf[j], vf[j], kt);
+      }
+    }
+  }
+  l += __shfl_xor(l, 32, 64);
+
+  // ---- the wave's partial to LDS: quad (dt, rq) of lane at [wave][dt * 4 + rq][lane] (16 B), m and l behind the quads
+  char* const mine = dsplit_smem + wave * PART;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int rq = 0; rq < 4; ++rq) {
+      const f32x4 v = {O[dt][rq * 4 + 0], O[dt][rq * 4 + 1], O[dt][rq * 4 + 2], O[dt][rq * 4 + 3]};
+      *(f32x4*)(mine + ((dt * 4 + rq) * 64 + lane) * 16) = v;
+    }
+  *(float*)(mine + 8 * 64 * 16 + lane * 4) = m;
+  *(float*)(mine + 8 * 64 * 16 + 256 + lane * 4) = l;
+  __syncthreads();
+
+  // ---- merge, waves 0 .. NW-1 in that order: every wave forms the row's maximum and sum, and its own QW quads of O
+  float ms[NW];
+  float M = -INFINITY;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    ms[w] = *(const float*)(dsplit_smem + w * PART + 8 * 64 * 16 + lane * 4);
+    M = fmaxf(M, ms[w]);
+  }
+  const float Mc = (M == -INFINITY ? 0.f : M) * kLog2e;
+  float L = 0.f;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    ms[w] = __builtin_amdgcn_exp2f(__builtin_fmaf(ms[w], kLog2e, -Mc));      // the partial's weight (m_w == -inf: 0)
+    L = __builtin_fmaf(*(const float*)(dsplit_smem + w * PART + 8 * 64 * 16 + 256 + lane * 4), ms[w], L);
+  }
+  const float inv = L > 0.f ? 1.0f / L : 0.f;
+  // (the row's batch and position are resolved again rather than kept in registers across the key loop)
+  int l31s = l31;
+  asm volatile("" : "+v"(l31s));
+  const RowInfo ro = row_info(p, l31s, first, rows);
+  if (!ro.valid) return;                            // (after the only barrier)
+  f16* const og = p.out + ((size_t)ro.qb * p.Nq + ro.t) * p.ldo + h * 64 + 4 * hi;
+  const int pl = p.ldo / 3;
+#pragma unroll
+  for (int i = 0; i < QW; ++i) {
+    const int qd = wave * QW + i;                   // quad dt * 4 + rq
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const f32x4 v = *(const f32x4*)(dsplit_smem + w * PART + (qd * 64 + lane) * 16);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(v[e], ms[w], acc[e]);
+    }
+    f16* const o = og + (qd >> 2) * 32 + (qd & 3) * 8;
+    if (p.out_mode >= 2) {   // wave-uniform: hi = T(o), lo = T(o - hi), planes [hi | lo | hi] (store_rows's rounding)
+      f16x4 vh, vl;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float v = acc[e] * inv;
+        vh[e] = Elt<T>::from_f32(v);
+        vl[e] = Elt<T>::from_f32(v - (float)vh[e]);
+      }
+      *(f16x4*)o = vh;
+      *(f16x4*)(o + pl) = vl;
+      *(f16x4*)(o + 2 * pl) = vh;
+    } else {
+      f16x4 v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = (f16)(acc[e] * inv);
+      *(f16x4*)o = v;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ one wave, one key tile
 // The output rows of attn_wave_kernel: store_rows_lds's transposition through 2 KiB of wave-private LDS (16 B per lane,
 // 64 contiguous bytes per row) for plain rows and, SPLIT, for the [hi | lo | hi] planes — the hi pass is written to planes
@@ -1452,6 +1624,18 @@ int launch_direct1(const AttnP<T>& p, hipStream_t s) {
   return VIDIL_OK;
 }
 
+template <typename T, int NW>
+int launch_dsplit(const AttnP<T>& p, hipStream_t s) {
+  VIDIL_REQUIRE((long long)p.H * p.n_kv < 0x7fffffffLL, "attention: H=%d x %d kv batches overflow the unit index", p.H, p.n_kv);
+  constexpr int smem = NW * (8 * 64 * 16 + 2 * 64 * 4);   // (attn_dsplit_kernel: NW x PART)
+  static std::atomic<unsigned long long> attr_set{0};   // (one bit per device that has the opt-in: vidil_lds_opt_in)
+  auto kern = attn_dsplit_kernel<T, NW>;
+  if (const int rc_ = vidil_lds_opt_in(attr_set, (const void*)kern, smem, "attention (key-split kernel)")) return rc_;
+  hipLaunchKernelGGL(kern, dim3(p.H * p.n_kv), dim3(NW * 64), smem, s, p);
+  VIDIL_CHECK_LAUNCH("attention/dsplit");
+  return VIDIL_OK;
+}
+
 template <typename T, int NKT>
 int launch_any(const AttnP<T>& p, int max_rows, hipStream_t s) {
   if constexpr (NKT == 7)
@@ -1470,7 +1654,7 @@ int launch_any(const AttnP<T>& p, int max_rows, hipStream_t s) {
 }
 
 template <typename T>
-int attention_dispatch(const AttnP<T>& p, int nkt, int max_rows, int Nk, hipStream_t s) {
+int attention_dispatch(const AttnP<T>& p, int nkt, int max_rows, int Nk, bool key_split, hipStream_t s) {
   switch (nkt) {
     case 1: return launch_any<T, 1>(p, max_rows, s);
     case 2: return launch_any<T, 2>(p, max_rows, s);
@@ -1499,6 +1683,16 @@ int attention_dispatch(const AttnP<T>& p, int nkt, int max_rows, int Nk, hipStre
     if (max_rows > 128) return launch_long<T, 8>(p, max_rows, s);
     return launch_long<T, 4>(p, max_rows, s);
   }
+  // the key-split form (attn_dsplit_kernel): at most 32 query rows per unit on fragment tiles, 16-bit or [hi | lo | hi] rows
+  if (key_split && p.tiled && max_rows <= 32 && p.out_mode != 1 && Nk <= kLongMaxNk) {
+    if (p.causal) {
+      vidil_set_error("attention: causal masks are not supported by the key-split form (Nk=%d > 768)", Nk);
+      return VIDIL_EUNSUP;
+    }
+    // four waves per unit (measured against eight — 64 / 4 units x 12 heads, 3 rows, bf16 —: 49 vs 117 us at 1,576 keys, 150 vs 308
+    // at 4,616; 11 vs 24 and 25 vs 65 with 4 units: at the 128 VGPRs that two resident 8-wave workgroups need the tile loop spills)
+    return launch_dsplit<T, 4>(p, s);
+  }
   vidil_set_error("attention: Nk=%d > 768 not supported by these kernels", Nk);
   return VIDIL_EUNSUP;
 }
@@ -1512,6 +1706,7 @@ extern "C" int vidil_attention(const void* q, const void* k, const void* vt, voi
                                int32_t dtype, int32_t out_dtype, void* stream) {
   VIDIL_REQUIRE(q && k && vt && out, "attention: null pointer");
   VIDIL_REQUIRE(Bq > 0 && H > 0 && Nq > 0 && Nk > 0, "attention: bad shape Bq=%d H=%d Nq=%d Nk=%d", Bq, H, Nq, Nk);
+  VIDIL_REQUIRE(kv_tiled >= 0 && kv_tiled <= 2, "attention: kv_tiled=%d (0: rows, 1: fragment tiles, 2: fragment tiles, key-split form allowed)", kv_tiled);
   if (kv_tiled) {
     VIDIL_REQUIRE(Tq_cap >= Nq && Tk_cap >= Nk && Tk_cap % 32 == 0,
                   "attention: tiled K/V need Tk_cap=%d >= Nk=%d and a multiple of 32", Tk_cap, Nk);
@@ -1551,7 +1746,7 @@ extern "C" int vidil_attention(const void* q, const void* k, const void* vt, voi
     const AttnP<T> p{(const T*)q, (const T*)k, (const T*)vt, (T*)out, kv_len, kv_index, group_start, Bq, H, Nq, Nk,
                      Tq_cap, Tk_cap, NP, kv_group, causal, causal_off, ldo, units, out_dtype == VIDIL_DT_FP8 ? 1 : (split3 ? 2 : 0),
                      kv_tiled ? 1 : 0, 1};
-    return attention_dispatch<T>(p, nkt, max_rows, Nk, (hipStream_t)stream);
+    return attention_dispatch<T>(p, nkt, max_rows, Nk, kv_tiled == 2, (hipStream_t)stream);
   });
 }
 

@@ -443,6 +443,13 @@ int check_args(const vidil_gemm_args& a) {
           VIDIL_REQUIRE(a.vt && a.Tk_cap >= a.t_off + a.T, "gemm/heads: bad v / Tk_cap");
       }
       VIDIL_REQUIRE(a.M % a.T == 0, "gemm/heads: M=%d not a multiple of T=%d", a.M, a.T);
+      {
+        // the scatter epilogues address a block's rows by a 32-bit byte offset from the block's first image (gemm_epilogue.inc:
+        // image x plane + token row, below 2^31): at most 256 rows per block, so 256 / T + 2 images of H x capacity x 128 bytes
+        const long long cap = a.Tq_cap > a.Tk_cap ? a.Tq_cap : a.Tk_cap;
+        VIDIL_REQUIRE((256 / a.T + 2) * (long long)a.H * cap * 128 < (1LL << 31),
+                      "gemm/heads: H=%d heads x capacity %lld with T=%d tokens per sequence overflow the epilogue's 32-bit offsets", a.H, cap, a.T);
+      }
       return VIDIL_OK;
     }
     case VIDIL_EPI_ARENA: {

@@ -284,9 +284,12 @@ def attention(q, k, vt, out, *, Bq, H, Nq, Nk, Tq_cap, Tk_cap, NP, kv_group=1, c
     """softmax(q k^T) v per head of 64 (vidil_attention).  Nk <= 768 keys in every form; Nk up to 16384 (a video's frames as
     one encoder sequence) in the long-key form, which needs more than 32 query rows per unit (max_group * Nq, kv_group * Nq,
     or Nq with kv_index), plain K / V (not kv_tiled), no causal mask and plain 16-bit output rows — anything else over 768 keys
-    raises VidilHipError("... not supported ...").  max_group is an upper bound: row tiles past a unit's rows return at once.
+    (but kv_tiled=2, below) raises VidilHipError("... not supported ...").  max_group is an upper bound: row tiles past a unit's rows return at once.
     group_start: int32 [n_kv+1] device prefix table (query batches per kv batch), with max_group.
-    kv_tiled: k / vt are fragment-tiled (gemm heads=dict(tiled=True)); at most 32 query rows per unit.
+    kv_tiled: k / vt are fragment-tiled (gemm heads=dict(tiled=True)); at most 32 query rows per unit.  False: plain rows; True:
+    fragment tiles, Nk <= 768; 2: fragment tiles with the key-split form allowed — up to 768 keys exactly the launches of True,
+    768 < Nk <= 16384 the key-split decode kernel (the beams of a caption search over a video's frame tokens: all three unit
+    forms, kv_len, plain or split3 rows; no causal mask).
     split3: ``out`` is [rows, 3*H*64] and receives the error-compensated operand rows [hi | lo | hi] (VIDIL_DT_SPLIT3)."""
     lib = _lib.load()
     ldo = ldo if ldo is not None else (3 if split3 else 1) * H * 64
@@ -297,7 +300,7 @@ def attention(q, k, vt, out, *, Bq, H, Nq, Nk, Tq_cap, Tk_cap, NP, kv_group=1, c
                               _ptr(kv_len, torch.int32, "attn.kv_len"), _ptr(kv_index, torch.int32, "attn.kv_index"),
                               _ptr(group_start, torch.int32, "attn.group_start"), n_kv, max_group,
                               Bq, H, Nq, Nk, Tq_cap, Tk_cap, NP,
-                              kv_group, int(bool(causal)), causal_off, ldo, int(bool(kv_tiled)), _dt(q, "attn.q"),
+                              kv_group, int(bool(causal)), causal_off, ldo, 2 if kv_tiled == 2 else int(bool(kv_tiled)), _dt(q, "attn.q"),
                               _dt(out, "attn.out", fp8_ok=True) | (DT_SPLIT3 if split3 else 0), _stream()), "attention")
     return out
 

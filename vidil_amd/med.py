@@ -486,7 +486,7 @@ class BertModel(PackedCache, nn.Module):
                     r0, r1 = (0, rows) if (b0, b1) == (0, cross.B) else (b0 * cross_group, b1 * cross_group)
                     K.attention(q[r0:r1], cross.k[i][b0:b1], cross.vt[i][b0:b1], o[r0 * T:r1 * T], Bq=r1 - r0, H=H, Nq=T, Nk=cross.Te,
                                 Tq_cap=T, Tk_cap=cross.Tk_cap, NP=cross.NP, kv_group=cross_group, kv_index=cross_index,
-                                group_start=cross_groups, max_group=mg, kv_tiled=cross.tiled, **ckl(r0, r1))
+                                group_start=cross_groups, max_group=mg, kv_tiled=self._cross_tiled(cross), **ckl(r0, r1))
                 K.gemm(o, d["co_w"], d["co_b"], out=tmp, resid=h32)
                 K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=h16, out32=h32)
             K.gemm(h16, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
@@ -494,15 +494,30 @@ class BertModel(PackedCache, nn.Module):
             K.layernorm(tmp, d["o_g"], d["o_bt"], eps, out16=h16, out32=h32)
         return h32, h16
 
-    #: vidil_attention's short kernels end here; past it only the long-key form exists, which needs MORE than 32 query rows per unit
+    #: vidil_attention's short kernels end here; past it the long-key form serves MORE than 32 query rows per unit on plain K / V,
+    #: the key-split form at most 32 on fragment tiles (a decoder session's: kv_tiled = 2)
     LONG_KEYS = 768
+
+    def _cross_tiled(self, cross):
+        """The ``kv_tiled`` selector of a cross-attention launch: 2 (key-split form allowed) for fragment tiles over more than
+        LONG_KEYS encoder states; otherwise what it always was, so launches over up to LONG_KEYS states are unchanged."""
+        return 2 if cross.tiled and cross.Te > self.LONG_KEYS else cross.tiled
 
     def _cross_bound(self, cross, Nq, cross_index, cross_group, cross_groups, cross_max_group):
         """The ``max_group`` bound of a cross-attention launch.  Up to LONG_KEYS encoder states it is the caller's; over more (a
-        video's frames concatenated as one encoder sequence) every launch must present more than 32 query rows per unit, so
-        the bound of the ``group_start`` form is rounded up to ceil(33 / Nq) — it is an upper bound, row tiles past a unit's
-        last row return at once — and the other forms are refused where they cannot reach 33 rows."""
+        video's frames concatenated as one encoder sequence) plain K / V are served by the long-key form, for which every launch
+        must present more than 32 query rows per unit, so the bound of the ``group_start`` form is rounded up to ceil(33 / Nq) — it
+        is an upper bound, row tiles past a unit's last row return at once — and the other forms are refused where they cannot
+        reach 33 rows.  Fragment tiles (a decoder session's) are served by the key-split form, at most 32 rows per unit: the
+        bound stays the caller's, and more rows are refused."""
         if cross.Te <= self.LONG_KEYS:
+            return cross_max_group
+        if cross.tiled:
+            rows = Nq * (cross_max_group if cross_groups is not None else 1 if cross_index is not None else cross_group)
+            if rows > 32:
+                raise K.VidilHipError(f"cross-attention over {cross.Te} > {self.LONG_KEYS} encoder states in fragment tiles serves at most "
+                                      f"32 query rows per unit (got {rows}): build the session with tiled_cross=False, whose launches "
+                                      "go to the long-key form")
             return cross_max_group
         if cross_groups is not None:
             return max(cross_max_group, -(-33 // Nq))
@@ -756,7 +771,7 @@ class BertModel(PackedCache, nn.Module):
                 r0, r1 = (0, rows) if (b0, b1) == (0, cross.B) else (b0 * cross_group, b1 * cross_group)
                 K.attention(q[r0:r1], cross.k[i][b0:b1], cross.vt[i][b0:b1], o[r0 * T:r1 * T], Bq=r1 - r0, H=H, Nq=T, Nk=cross.Te,
                             Tq_cap=T, Tk_cap=cross.Tk_cap, NP=cross.NP, kv_group=cross_group, kv_index=cross_index,
-                            group_start=cross_groups, max_group=mg, kv_tiled=cross.tiled, **ckl(r0, r1))
+                            group_start=cross_groups, max_group=mg, kv_tiled=self._cross_tiled(cross), **ckl(r0, r1))
             residual_gemm(o, d["co_w"], d["co_b"], d["co_g"], d["co_bt"])
             consumer("fc1", i, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
             residual_gemm(inter, d["o_w"], d["o_b"], d["o_g"], d["o_bt"])
