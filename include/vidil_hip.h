@@ -292,6 +292,18 @@ int vidil_attention(const void* q, const void* k, const void* vt, void* out,
 /*   a multiple of 32): the decode steps' cross-attention, at most 32 query rows */
 /*   per unit — Q (f32, in place) and the probabilities are split, K / V are    */
 /*   what the tiles hold (S = K.Q_lo + K.Q_hi, O = V.P_lo + V.P_hi).            */
+/*  arith == 2: arith 1 (dense forms, f32 K / V rows: kv16 == 0, anc == NULL)   */
+/*   with a RELATIVE-POSITION BIAS: after S = K.(Q*scale)^T and before the key  */
+/*   limit, rel_bias[h*rel_bias_ld + rel_off + key - t] is added (f32, not      */
+/*   scaled) to the score of (row t of its query batch, key) - MPNet's shared   */
+/*   T5-bucketed bias, which depends on key - t alone.  rel_off >= Nq - 1 and   */
+/*   rel_off + Nk <= rel_bias_ld; only [rel_off-(Nq-1), rel_off+Nk-1] of a      */
+/*   head's table is read.  Masked keys stay masked.  A unit of one query row   */
+/*   runs on the general kernel.  The fields rel_bias, rel_bias_ld and rel_off  */
+/*   were APPENDED to the struct without an ABI bump: they are read ONLY when   */
+/*   arith == 2, a value no caller built against the struct that ended at kv16  */
+/*   passes (it was VIDIL_EINVAL), so the library never reads past such a       */
+/*   caller's struct.                                                           */
 /* replaces (in that mode): models/vit.py:75-83; models/med.py:178-220; HF     */
 /* CLIPAttention.                                                              */
 /* ------------------------------------------------------------------------ */
@@ -313,8 +325,11 @@ typedef struct {
   const int32_t* anc;
   int32_t anc_ld, arena_rows;
   float scale;
-  int32_t arith;   /* 0: f32 arithmetic; 1: split-operand 16-bit MFMA (ABI 10, see above) */
+  int32_t arith;   /* 0: f32 arithmetic; 1: split-operand 16-bit MFMA (ABI 10, see above); 2: 1 + rel_bias */
   int32_t kv16;    /* arith 1 only: k / v are dtype16 fragment tiles [n_kv][H][kv_rows/32][2048] */
+  const float* rel_bias;   /* arith 2 only (not read otherwise): [H][rel_bias_ld] f32 table */
+  int32_t rel_bias_ld;     /* arith 2 only: floats between two heads' tables */
+  int32_t rel_off;         /* arith 2 only: index of distance 0 (key == t) in a head's table */
 } vidil_attn_f32_args;
 int vidil_attention_f32(const vidil_attn_f32_args* args, void* stream);
 

@@ -70,6 +70,7 @@ class AttnF32Args(C.Structure):
         ("anc_ld", C.c_int32), ("arena_rows", C.c_int32),
         ("scale", C.c_float),
         ("arith", C.c_int32), ("kv16", C.c_int32),
+        ("rel_bias", C.c_void_p), ("rel_bias_ld", C.c_int32), ("rel_off", C.c_int32),     # read only when arith == 2
     ]
 
 

@@ -1783,6 +1783,8 @@ struct AttnF32P {
   const int32_t* anc;          // arena form
   int anc_ld, arena_rows;
   float scale;
+  const float* rel_bias;       // arith = 2: per-head relative-position table, score(t, key) += rel_bias[h * rel_bias_ld + rel_off + key - t]
+  int rel_bias_ld, rel_off;
 };
 
 template <typename T16>
@@ -2074,7 +2076,16 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
 // MFMAs): K in the GEMMs' XOR-swizzled 128-byte rows (ds_read_b128 fragments), V row-major in [d / 16][32 keys][16 d] blocks
 // that ds_read_b64_tr_b16 reads transposed (the streamed tower kernel's layout: no key permutation, no 2-byte scatter).
 // 24 MFMAs of v_mfma_f32_32x32x16 per 32 x 32 tile where the f32-input form issues 64 instructions of twice the latency.
-template <typename T16, int NW>      // NW waves = NW x 32 virtual query rows of a unit per workgroup (launched with NW = 4)
+//
+// RELB (arith = 2): a learned relative-position bias joins every score before the key-limit mask — S(t, key) += table[h][rel_off +
+// key - t], an unscaled f32 add (MPNet's attention; the bias is Toeplitz in (t, key), so Nq + Nk - 1 floats per head carry it).  A
+// lane owns one query row t and, per tile, the keys k0 + 4 * hi + 8 * q + (0..3), q = 0..3: four runs of four consecutive floats
+// of its head's table, read through the vector cache (lanes of consecutive rows read addresses that step DOWN by one float, so a
+// half-wave's reads of one run fall inside 35 consecutive floats, and a head's whole window — 3 KiB for the sentence encoder —
+// stays cache resident).  The loads are issued before the tile's twelve K.Q^T MFMAs and consumed after them.  Keys past Nk - 1
+// are clamped onto Nk - 1 (masked below anyway), so only [rel_off - (Nq - 1), rel_off + Nk - 1] of a head's table is read.
+// RELB = false compiles to the kernel as it was: every line of the form is under `if constexpr`.
+template <typename T16, int NW, bool RELB = false>      // NW waves = NW x 32 virtual query rows of a unit per workgroup (launched with NW = 4)
 __global__ __launch_bounds__(NW * 64, 3) void attn_split_kernel(const AttnF32P p) {
   using x8 = typename Elt<T16>::x8;
   using x4 = typename Elt<T16>::x4;
@@ -2151,6 +2162,9 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_split_kernel(const AttnF32P p
     const s16x8 both = __builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(x8, both);
   };
+  // RELB: this lane's row of the head's table, based so that index `key` is the bias of (ri.t, key)
+  const float* brow = nullptr;
+  if constexpr (RELB) brow = p.rel_bias + (size_t)h * p.rel_bias_ld + (p.rel_off - ri.t);
   // smallest key limit of the wave's rows: tiles that end below it need no mask
   int kmin = ri.klim;
 #pragma unroll
@@ -2184,6 +2198,16 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_split_kernel(const AttnF32P p
     __syncthreads();
     if (k0 + 32 < p.Nk) fetch(k0 + 32);    // (in flight under this tile's MFMAs)
     if (!wave_live) continue;
+    float rb[RELB ? 16 : 1];
+    if constexpr (RELB) {
+      if (k0 + 32 <= p.Nk) {               // (uniform: every key of the tile exists)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rb[r] = brow[k0 + (r & 3) + 8 * (r >> 2) + 4 * hi];
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rb[r] = brow[min(k0 + (r & 3) + 8 * (r >> 2) + 4 * hi, p.Nk - 1)];
+      }
+    }
     // ---- S^T[key][row]: corrections first, the leading product last
     f32x16 S;
 #pragma unroll
@@ -2196,6 +2220,10 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_split_kernel(const AttnF32P p
       S = Elt<T16>::mfma32(kl, qh[ks], S);
       S = Elt<T16>::mfma32(kh, ql[ks], S);
       S = Elt<T16>::mfma32(kh, qh[ks], S);
+    }
+    if constexpr (RELB) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) S[r] += rb[r];
     }
     // ---- online softmax: S[r] belongs to key k0 + (r & 3) + 8 * (r >> 2) + 4 * hi of this lane's row.  The reference m moves
     // only when a tile outgrows it by kLazy (a wave-uniform decision: softmax_tile above has the argument)
@@ -2449,6 +2477,18 @@ extern "C" int vidil_attention_f32(const vidil_attn_f32_args* a, void* stream) {
   p.Bq = a->Bq; p.H = a->H; p.Nq = a->Nq; p.Nk = a->Nk; p.kv_rows = a->kv_rows; p.kv_group = a->kv_group;
   p.causal = a->causal; p.causal_off = a->causal_off; p.n_kv = a->n_kv;
   p.anc = a->anc; p.anc_ld = a->anc_ld; p.arena_rows = a->arena_rows; p.scale = a->scale;
+  p.rel_bias = nullptr; p.rel_bias_ld = 0; p.rel_off = 0;
+  if (a->arith == 2) {
+    // the relative-position-bias form: the ONLY value of arith for which the three fields behind kv16 are read (a caller built
+    // against the struct as it ended at kv16 never passes it, so the library never reads past that caller's struct)
+    VIDIL_REQUIRE(a->anc == nullptr, "attention_f32 (rel_bias): dense forms only (anc must be NULL)");
+    VIDIL_REQUIRE(a->kv16 == 0, "attention_f32 (rel_bias): f32 K / V rows only (kv16 must be 0)");
+    VIDIL_REQUIRE(a->rel_bias != nullptr && ((uintptr_t)a->rel_bias & 3) == 0, "attention_f32 (rel_bias): rel_bias is NULL or not 4-byte aligned");
+    VIDIL_REQUIRE(a->rel_off >= a->Nq - 1, "attention_f32 (rel_bias): rel_off=%d < Nq - 1 = %d", a->rel_off, a->Nq - 1);
+    VIDIL_REQUIRE((long long)a->rel_off + a->Nk <= (long long)a->rel_bias_ld, "attention_f32 (rel_bias): rel_off=%d + Nk=%d > rel_bias_ld=%d",
+                  a->rel_off, a->Nk, a->rel_bias_ld);
+    p.rel_bias = a->rel_bias; p.rel_bias_ld = a->rel_bias_ld; p.rel_off = a->rel_off;
+  }
   hipStream_t s = (hipStream_t)stream;
   const bool bf = a->dtype16 == VIDIL_DT_BF16;
   if (a->anc != nullptr) {
@@ -2503,21 +2543,24 @@ extern "C" int vidil_attention_f32(const vidil_attn_f32_args* a, void* stream) {
     VIDIL_CHECK_LAUNCH("attention_f32 (split, one row per unit)");
     return VIDIL_OK;
   }
-  if (a->arith == 1) {
+  if (a->arith == 1 || a->arith == 2) {
     // split-operand form on f32 Q / K / V in place: any number of rows per unit (a unit of a few rows leaves three of the four
-    // waves without rows: they still stage)
+    // waves without rows: they still stage).  arith 2 (relative-position bias) comes here with one row per unit too
     VIDIL_REQUIRE((a->out_mode >= 2 ? a->ldo % 12 == 0 : a->ldo % 4 == 0) && ((uintptr_t)a->out & 15) == 0,
                   "attention_f32 (split): output rows must allow 8-byte (split3) / 16-byte (f32) stores");
     // 4 waves (128 rows) per workgroup. An 8-wave form (one staging of a unit's K / V serves up to 256 rows) measured 2 - 12 %
     // slower on a tower's 197 rows at 512 ... 3584 images and 0.8 % slower end to end (round 5): 59 of its 256
     // rows are padding, and the staging it saves was not what bounds the kernel
     const dim3 gridm((max_rows + 127) / 128, a->H, units);
-    if (bf) hipLaunchKernelGGL((attn_split_kernel<bf16, 4>), gridm, dim3(256), 0, s, p);
+    if (a->arith == 2) {
+      if (bf) hipLaunchKernelGGL((attn_split_kernel<bf16, 4, true>), gridm, dim3(256), 0, s, p);
+      else hipLaunchKernelGGL((attn_split_kernel<f16, 4, true>), gridm, dim3(256), 0, s, p);
+    } else if (bf) hipLaunchKernelGGL((attn_split_kernel<bf16, 4>), gridm, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((attn_split_kernel<f16, 4>), gridm, dim3(256), 0, s, p);
     VIDIL_CHECK_LAUNCH("attention_f32 (split)");
     return VIDIL_OK;
   }
-  VIDIL_REQUIRE(a->arith == 0, "attention_f32: arith=%d (0: f32, 1: split-operand)", a->arith);
+  VIDIL_REQUIRE(a->arith == 0, "attention_f32: arith=%d (0: f32, 1: split-operand, 2: split-operand + relative-position bias)", a->arith);
   // units of more than 8 query rows (the towers, the ITM encoder, prompt passes): the f32-MFMA kernel, 128 rows per workgroup;
   // a few rows per unit (the decode steps' cross-attention: 3 beams per image): the VALU kernel, which skips idle row groups
   if (max_rows > 8 && (a->out_mode >= 2 ? a->ldo % 12 == 0 : a->ldo % 4 == 0) && ((uintptr_t)a->out & 15) == 0) {   // (16-B / 8-B row stores)

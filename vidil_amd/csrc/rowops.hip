@@ -10,22 +10,26 @@ namespace {
 
 // One wave per row; D/64 elements per lane, processed as float4 where D%256==0
 // is not required: lane handles elements lane*4 + 256*i (+0..3).
-template <typename T, int VPL>  // float4 vectors per lane: D = 256*VPL
+// HALF (D = 128, VPL = 1: a small text stack): lanes 0-31 hold the row, the others add zeros to the two sums and store nothing.
+template <typename T, int VPL, bool HALF = false>  // float4 vectors per lane: D = 256*VPL (HALF: 128)
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t x_stride,
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps, int M,
                                                         T* __restrict__ out16, float* __restrict__ out32, int split3) {
   using x4 = typename std::conditional<sizeof(T) == 1, uint32_t, typename Elt<typename std::conditional<sizeof(T) == 1, f16, T>::type>::x4>::type;
-  constexpr int D = 256 * VPL;
+  static_assert(!HALF || VPL == 1, "HALF is the D = 128 form of VPL = 1");
+  constexpr int D = HALF ? 128 : 256 * VPL;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
+  const bool holds = !HALF || lane < 32;
   const float* xr = x + (size_t)row * x_stride;
   f32x4 v[VPL];
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
-    v[i] = __builtin_nontemporal_load((const f32x4*)(xr + i * 256 + lane * 4));   // streamed once: do not keep in L2
+    if (holds) v[i] = __builtin_nontemporal_load((const f32x4*)(xr + i * 256 + lane * 4));   // streamed once: do not keep in L2
+    else v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
   }
   const float mean = wave_sum(s) * (1.0f / D);
@@ -35,11 +39,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float d = v[i][e] - mean;
-      ss += d * d;
+      ss += holds ? d * d : 0.f;
     }
   }
   const float var = wave_sum(ss) * (1.0f / D);
   const float rstd = 1.0f / sqrtf(var + eps);
+  if (!holds) return;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int c = i * 256 + lane * 4;
@@ -252,13 +257,14 @@ static int layernorm_launch(const float* x, int64_t x_stride, const float* gamma
                             T* out16, float* out32, hipStream_t s, int split3 = 0) {
   dim3 grid((M + 3) / 4), block(256);
   switch (D) {
+    case 128: hipLaunchKernelGGL((layernorm_kernel<T, 1, true>), grid, block, 0, s, x, x_stride, gamma, beta, eps, M, out16, out32, split3); break;
     case 256: hipLaunchKernelGGL((layernorm_kernel<T, 1>), grid, block, 0, s, x, x_stride, gamma, beta, eps, M, out16, out32, split3); break;
     case 512: hipLaunchKernelGGL((layernorm_kernel<T, 2>), grid, block, 0, s, x, x_stride, gamma, beta, eps, M, out16, out32, split3); break;
     case 768: hipLaunchKernelGGL((layernorm_kernel<T, 3>), grid, block, 0, s, x, x_stride, gamma, beta, eps, M, out16, out32, split3); break;
     case 1024: hipLaunchKernelGGL((layernorm_kernel<T, 4>), grid, block, 0, s, x, x_stride, gamma, beta, eps, M, out16, out32, split3); break;
     case 1280: hipLaunchKernelGGL((layernorm_kernel<T, 5>), grid, block, 0, s, x, x_stride, gamma, beta, eps, M, out16, out32, split3); break;
     default:
-      vidil_set_error("layernorm: D=%d not supported (256/512/768/1024/1280)", D);
+      vidil_set_error("layernorm: D=%d not supported (128/256/512/768/1024/1280)", D);
       return VIDIL_EUNSUP;
   }
   VIDIL_CHECK_LAUNCH("layernorm");

@@ -319,13 +319,16 @@ def _f32_view(t, what):
 
 
 def attention_f32(q, k, v, out, *, Bq, H, Nq, Nk, kv_rows=None, kv_group=1, causal=False, causal_off=0, kv_len=None, kv_index=None,
-                  group_start=None, max_group=0, scale=0.125, split3=None, anc=None, arena_rows=0, arith=0, kv16=False, planes=3):
+                  group_start=None, max_group=0, scale=0.125, split3=None, anc=None, arena_rows=0, arith=0, kv16=False, planes=3,
+                  rel_bias=None, rel_off=None):
     """softmax(q k^T * scale) v in f32 (the attention of the parity precision mode; vidil_attention_f32).
 
     arith: 0 = plain f32 arithmetic; 1 = split-operand 16-bit MFMA (every operand as hi + lo, three products per contraction:
     ~1e-6 of the logit scale from f32 arithmetic at a fifth of its cost; dense forms — the arena form always runs in f32).
     kv16 (arith 1): ``k`` / ``v`` are 16-bit FRAGMENT TILES [n_kv, H, kv_rows, 64] (project_cross_kv(tiled=True)) instead of f32
     rows — the decode steps' cross-attention, at most 32 query rows per unit; Q and the probabilities are split, K / V as stored.
+    rel_bias (+ rel_off): an f32 table [H, ld] — selects arith = 2, the split-operand form with ``rel_bias[h, rel_off + key - t]``
+    added (unscaled) to the score of (row t of its query batch, key); rel_off >= Nq - 1, rel_off + Nk <= ld, dense f32 forms only.
 
     q, k, v: f32 matrices — typically COLUMN SLICES of the row-major output of a projection GEMM (``qkv32[:, :C]``, ``[:, C:2*C]``,
     ``[:, 2*C:]``): row stride and column offset are taken from the views, head h occupies columns h*64 .. h*64+63.
@@ -365,6 +368,13 @@ def attention_f32(q, k, v, out, *, Bq, H, Nq, Nk, kv_rows=None, kv_group=1, caus
     a.scale = float(scale)
     a.arith = 0 if anc is not None else int(arith)          # (the arena form has no split-operand kernel: f32 arithmetic)
     a.kv16 = 1 if kv16 else 0
+    if rel_bias is not None:
+        if rel_off is None or rel_bias.dim() != 2 or rel_bias.shape[0] != H:
+            raise VidilHipError(f"attention_f32: rel_bias must be an f32 [H, ld] table given with rel_off, got shape {tuple(rel_bias.shape)} "
+                                f"rel_off {rel_off}")
+        a.rel_bias, a.rel_bias_ld = _f32_view(rel_bias, "attention_f32.rel_bias")
+        a.rel_off = int(rel_off)
+        a.arith = 2                                         # (with anc or kv16 the library refuses it: no such form)
     check(_lib.load().vidil_attention_f32(C.byref(a), _stream()), "attention_f32")
     return out
 

@@ -548,12 +548,17 @@ class BertModel(PackedCache, nn.Module):
         return [(b0, min(B, b0 + n)) for b0 in range(0, B, n)]
 
     def _run_layers_parity(self, p, h32, h3, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len, cross, cross_index,
-                           cross_group, cross_groups, cross_max_group, ws, arena, arena_slot_stride, n_layers=None, cross_kv_len=None):
+                           cross_group, cross_groups, cross_max_group, ws, arena, arena_slot_stride, n_layers=None, cross_kv_len=None,
+                           rel_bias=None, rel_off=None):
         """run_layers in the parity precision mode: ``h3`` [rows*T, 3C] carries the hidden states as [hi | lo | hi]
         operand rows, every GEMM runs against [W_hi | W_hi | W_lo] with K tripled, LayerNorm / attention write split rows
         directly and the GELU output goes through f32 + vidil_split3_f32.  Same launch sequence otherwise.
         n_layers: only the first n layers (encode_cls_parity runs the last itself); ws["planes_h"] then tells it how many
-        planes of ``h3`` the last of them wrote."""
+        planes of ``h3`` the last of them wrote.
+        rel_bias / rel_off (vidil_amd/sentence.py, which runs this sequence as the layers of MPNet): a relative-position bias table
+        for the block self-attention of every layer (kernels.attention_f32's arguments; the f32-row attention kinds only)."""
+        if rel_bias is not None and (not parity_attention_f32(self) or arena is not None or cross is not None):
+            raise K.VidilHipError("_run_layers_parity: rel_bias serves the f32-row self-attention of a stack without cross-attention or arena")
         if cross_kv_len is not None:
             raise K.VidilHipError("_run_layers_parity: cross_kv_len (masked cross-attention) is not built for the parity precision mode")
         cfg = self.config
@@ -620,7 +625,7 @@ class BertModel(PackedCache, nn.Module):
                                     arena_rows=arena.rows, planes=planes_h)
                 else:
                     K.attention_f32(qkv32[:, :C], qkv32[:, C:2 * C], qkv32[:, 2 * C:], o3, Bq=rows, H=H, Nq=T, Nk=T, causal=causal,
-                                    kv_len=kv_len, arith=arith, planes=planes_h)
+                                    kv_len=kv_len, arith=arith, planes=planes_h, rel_bias=rel_bias, rel_off=rel_off)
                     if arena is not None:   # the prompt's K / V in the arena: position t, slot r * arena_slot_stride
                         blk = qkv32.view(rows, T, 3 * C)
                         arena.k[i][:T, 0:rows * arena_slot_stride:arena_slot_stride] = blk[:, :, C:2 * C].permute(1, 0, 2)

@@ -292,3 +292,92 @@ def random_prefix_prompt_lines(visual_tokens, frame_captions_filtered, frame_cap
             lines.append(json.dumps(body))
             line_to_video[len(lines) - 1] = video_name
     return lines, line_to_video
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# In-context selection (generate_prompts_random_prefix_in_context_selection.py:131-287): the few-shot examples of every
+# prompt are the N support examples closest to the query, by the cosine of sentence embeddings (vidil_amd/sentence.py).
+
+COMPARING_TARGETS = ("question", "caption", "caption_asr")      # (any other value compares the whole strings)
+
+
+def comparing_text(text, comparing_target):
+    """What of a rendered example / query is embedded (:132-142,182-192): the question line, the frame-caption line, the frame
+    captions up to '\\nVideo Caption' (subtitles included), or — any other target — the whole string."""
+    if comparing_target == "question":
+        return text.split("Question: ")[1].split("\n")[0].strip()
+    if comparing_target == "caption":
+        return text.split("Frame Captions: ")[1].split("\n")[0].strip()
+    if comparing_target == "caption_asr":
+        return text.split("Frame Captions: ")[1].split("\nVideo Caption")[0].strip()
+    return text
+
+
+def select_from_support_set(model, in_context_examples_embeddings, in_context_examples, query_instance_str, N=5,
+                            comparing_target="question"):
+    """:131-148 — the N support examples closest to the query, THE HIGHEST LAST (all of them, lowest first, when N exceeds the
+    support set: ``argsort(...)[-N:]``).  ``model``: a SentenceEncoder (``encode``); ``query_instance_str``: one rendered query or
+    a list of them — then a list of selections, the queries embedded in batches.  Equal cosines are ordered by index (the lower
+    index counts as closer), where numpy's argsort leaves the order open."""
+    from .sentence import closest
+
+    single = isinstance(query_instance_str, str)
+    texts = [comparing_text(q, comparing_target) for q in ([query_instance_str] if single else query_instance_str)]
+    if not texts:
+        return []
+    _, idx = closest(model.encode(texts, convert_to_tensor=True), in_context_examples_embeddings, N)
+    picked = [[in_context_examples[j] for j in reversed(row)] for row in idx.cpu().tolist()]
+    return picked[0] if single else picked
+
+
+def in_context_selection_prompt_lines(visual_tokens, frame_captions_filtered, frame_captions_unfiltered, N, instruction_line,
+                                      in_context_examples, config, video_2_question_answer_pairs=None, video_2_asr=None,
+                                      comparing_target="question", model=None):
+    """``save_prompt_lines_with_in_context_selection`` (:150-287) without its file output: per video — per (video, question) for
+    the qa task — a request body whose prefix is the instruction line and the N closest support examples (highest last), and the
+    line -> video map.  The support embeddings are computed once; the queries are rendered first and embedded together instead of
+    one ``encode`` call each (the selection is the same).  Captions fall back as in the other generators; an empty subtitle list,
+    or one that joins to '' or ' ', becomes 'no subtitle.'; the vlep task trims and caps subtitles at 1,024 characters.
+    Like the script, every query is rendered twice — by a throw-away ``Prompt("", 42)`` for the comparison and by a
+    ``Prompt(prefix, 42)`` (which re-seeds the global ``random``) for the request — in the script's order, so list-valued original
+    captions are shuffled exactly as there."""
+    import json
+    import random
+
+    if model is None:
+        raise ValueError("in_context_selection_prompt_lines: model (a SentenceEncoder) is required")
+    dummy = Prompt("", seed=42)
+    support = model.encode([comparing_text(e, comparing_target) for e in in_context_examples], convert_to_tensor=True)
+    task = config["prompt_task"]
+    queries, tails, keys = [], [], []
+    for video_name, obj in visual_tokens.items():
+        captions = frame_captions_filtered
+        if video_name not in frame_captions_filtered:
+            if not config["caption_all_video"] or video_name not in frame_captions_unfiltered:
+                continue
+            captions = frame_captions_unfiltered
+        asr = None
+        if video_2_asr is not None and video_name in video_2_asr:
+            asr = _subtitle_text(video_2_asr[video_name], task)
+            if asr in ("", " "):
+                asr = "no subtitle."
+        if task == "qa":
+            if video_name not in video_2_question_answer_pairs:
+                continue
+            items = [(item["question"], item["answer"], (video_name, qidx))
+                     for qidx, item in enumerate(video_2_question_answer_pairs[video_name])]
+        else:
+            items = [(None, None, video_name)]
+        for question, answer, key in items:
+            queries.append(dummy.construct_prompt(video_name, obj, captions, config, question, answer, asr))
+            random.seed(42)        # what the script's Prompt(prefix, seed=42) does before it renders the request
+            tails.append(dummy.construct_prompt(video_name, obj, captions, config, question, answer, asr))
+            keys.append(key)
+    lines, line_to_video = [], {}
+    selections = select_from_support_set(model, support, in_context_examples, queries, N=N, comparing_target=comparing_target)
+    for tail, key, chosen in zip(tails, keys, selections):
+        body = config["request_body"]
+        body["prompt"] = "\n\n".join([instruction_line] + chosen) + "\n\n" + tail      # (the prompt is prefix + rendering)
+        lines.append(json.dumps(body))
+        line_to_video[len(lines) - 1] = key
+    return lines, line_to_video

@@ -154,3 +154,86 @@ def refuse_synthetic_with_checkpoint(tokenizer, pretrained):
     if pretrained and getattr(tokenizer, "is_synthetic", False) and not getattr(tokenizer, "allow_pretrained", False):
         raise RuntimeError("a pretrained checkpoint needs the real bert-base-uncased tokenizer, not SyntheticBertTokenizer "
                            "(unset VIDIL_TOKENIZER=synthetic / pass a real tokenizer, or set $VIDIL_BERT_VOCAB)")
+
+
+# ---------------------------------------------------------------------------------------------- sentence encoder (MPNet)
+S_BOS, S_PAD, S_EOS, S_UNK = 0, 1, 2, 3          # '<s>', '<pad>', '</s>', '<unk>': the first four lines of an MPNet vocab.txt
+SENTENCE_MODEL = "sentence-transformers/all-mpnet-base-v2"
+
+
+class SyntheticSentenceTokenizer:
+    """The id-preserving stand-in for the sentence encoder (tests and benchmarks with random weights): token id N <-> the
+    word ``wN``, MPNet's specials at 0 .. 3, ``<s> ... </s>`` around every sentence.  Used on explicit request only;
+    ``refuse_synthetic_with_checkpoint`` refuses it together with a pretrained directory."""
+    bos_token_id = cls_token_id = S_BOS
+    pad_token_id = S_PAD
+    eos_token_id = sep_token_id = S_EOS
+    unk_token_id = S_UNK
+    is_synthetic = True
+
+    def __init__(self, vocab_size=30527, allow_pretrained=False):
+        self.vocab_size = vocab_size
+        self.allow_pretrained = allow_pretrained
+
+    def _word_id(self, w):
+        if len(w) > 1 and w[0] == "w" and w[1:].isdigit() and 4 <= int(w[1:]) < self.vocab_size:
+            return int(w[1:])
+        return S_UNK
+
+    def encode_one(self, text, max_length=None, truncation=False):
+        ids = [S_BOS] + [self._word_id(w) for w in text.lower().split()] + [S_EOS]
+        if truncation and max_length is not None and len(ids) > max_length:
+            ids = ids[: max_length - 1] + [S_EOS]
+        return ids
+
+    def __call__(self, text, truncation=False, max_length=None, **_):
+        if isinstance(text, str):
+            return Encoding(input_ids=self.encode_one(text, max_length, truncation))
+        return Encoding(input_ids=[self.encode_one(t, max_length, truncation) for t in text])
+
+    def decode(self, ids, skip_special_tokens=False):
+        names = {S_BOS: "<s>", S_PAD: "<pad>", S_EOS: "</s>", S_UNK: "<unk>"}
+        ids = [int(i) for i in (ids.tolist() if torch.is_tensor(ids) else ids)]
+        return " ".join(names[i] if i in names else f"w{i}" for i in ids if not (skip_special_tokens and i in names))
+
+
+def init_sentence_tokenizer(vocab_file=None):
+    """The tokenizer of sentence-transformers' all-mpnet-base-v2: HF ``MPNetTokenizer`` — lower-casing WordPiece with ``<s>`` = 0,
+    ``<pad>`` = 1, ``</s>`` = 2, ``<unk>`` = 3 and ``<s> ... </s>`` around a sentence.  Unknown words map to ``[UNK]`` when the
+    vocabulary has that entry (the released vocab.txt: MPNet's four specials in front of BERT's list, and the released
+    tokenizer configuration names ``[UNK]``), else to ``<unk>``.
+
+    Sources, in order: ``vocab_file`` / $VIDIL_MPNET_VOCAB (a vocab.txt; a wrong path raises), the local HF cache
+    (``local_files_only=True``).  There is NO hub fallback: nothing here opens a connection.  Anything else raises;
+    ``SyntheticSentenceTokenizer`` is the explicit stand-in."""
+    vocab_file = vocab_file or os.environ.get("VIDIL_MPNET_VOCAB")
+    from transformers import MPNetTokenizer
+
+    if vocab_file:
+        if not os.path.isfile(vocab_file):
+            raise FileNotFoundError(f"init_sentence_tokenizer: vocabulary file {vocab_file!r} does not exist")
+        with open(vocab_file, encoding="utf-8") as f:
+            vocab = {w.rstrip("\n"): i for i, w in enumerate(f)}
+        want = {"<s>": S_BOS, "<pad>": S_PAD, "</s>": S_EOS, "<unk>": S_UNK}
+        if any(vocab.get(w) != i for w, i in want.items()):
+            raise RuntimeError(f"init_sentence_tokenizer: {vocab_file!r} is not an MPNet vocabulary (its first four lines must be "
+                               "<s>, <pad>, </s>, <unk>)")
+        unk = "[UNK]" if "[UNK]" in vocab else "<unk>"
+        try:
+            tok = MPNetTokenizer(vocab=vocab, unk_token=unk)               # transformers 5.x
+        except TypeError:
+            tok = MPNetTokenizer(vocab_file=vocab_file, unk_token=unk)     # transformers 4.x
+        if len(tok) != len(vocab):
+            raise RuntimeError(f"init_sentence_tokenizer: MPNetTokenizer holds {len(tok)} entries, {vocab_file!r} has {len(vocab)}")
+        return tok
+    try:
+        tok = MPNetTokenizer.from_pretrained(SENTENCE_MODEL, local_files_only=True)
+        # (transformers 5.x answers an EMPTY cache with a tokenizer of its five special tokens instead of an error)
+        if len(tok) < 30527 or [tok.convert_tokens_to_ids(w) for w in ("<s>", "<pad>", "</s>", "<unk>")] != [S_BOS, S_PAD, S_EOS, S_UNK]:
+            raise RuntimeError(f"the local HF cache yields a tokenizer of {len(tok)} entries, not all-mpnet-base-v2's vocabulary")
+        return tok
+    except Exception as e:
+        raise RuntimeError(
+            "init_sentence_tokenizer: the all-mpnet-base-v2 vocabulary is not available (no vocab_file, no $VIDIL_MPNET_VOCAB, "
+            "nothing in the local HF cache) and it is never downloaded here.  Pass its vocab.txt, or — for benchmarks / tests with "
+            "random weights only — the id-preserving stand-in: tokenizer=SyntheticSentenceTokenizer().") from e

@@ -69,6 +69,22 @@ def accuracy(result, annotations):
     return sum(1 for k in common if pred[k] == truth[k]) / len(common)
 
 
+def map_answers(result, answer_list, encoder):
+    """eval_video_qa_result.py:172-196: every GENERATED answer of ``result`` ([{question_id, answer}]) replaced by the entry of
+    ``answer_list`` whose sentence embedding has the largest cosine with the answer's (``encoder``: a vidil_amd.sentence
+    SentenceEncoder) — what the reference scores for ``inference='generate'``.  Returns [{question_id, answer}], ready for
+    ``accuracy``.  Among equal cosines the entry of lowest index wins (numpy's argmax: the first maximum)."""
+    from .sentence import closest
+
+    result, answer_list = list(result), list(answer_list)
+    if not result:
+        return []
+    answers = encoder.encode(answer_list, convert_to_tensor=True)
+    preds = encoder.encode([r["answer"] for r in result], convert_to_tensor=True)
+    _, idx = closest(preds, answers, 1)
+    return [{"question_id": r["question_id"], "answer": answer_list[j]} for r, (j,) in zip(result, idx.cpu().tolist())]
+
+
 # ---------------------------------------------------------------------------------------------- evaluation
 def _video_batches(videos):
     if torch.is_tensor(videos):
@@ -80,12 +96,14 @@ def _video_batches(videos):
 
 @torch.no_grad()
 def evaluation(model, videos, questions, question_ids, video_of_question, *, answer_list=None, inference="rank", k_test=64,
-               video_representation="concat_frame", videos_per_block=None, timings=None, details=None):
+               video_representation="concat_frame", videos_per_block=None, timings=None, details=None, map_with=None):
     """train_vqa_video.py:66-104 for world size 1.  ``model``: a BLIP_Video_VQA on the GPU; ``videos``: f32 [V,N,3,S,S]
     (normalised) or an iterable of such batches — uint8 [b,N,S,S,3] batches take the fused preprocessing —, every video the same
     N; ``questions``: list[str] (already ``pre_question``-ed), ``question_ids`` their ids, ``video_of_question`` int [Q] the
     index of each question's video in ``videos``.  ``answer_list`` (inference='rank'): list[str], ``k_test`` of them scored in
     stage 2.  ``video_representation='single_frame'``: frame int(N/2) alone (:83-86).
+    ``map_with`` (inference='generate'; a vidil_amd.sentence SentenceEncoder, with ``answer_list``): the generated answers are
+    mapped onto ``answer_list`` by ``map_answers`` — the result the reference's eval_video_qa_result.py scores.
     Returns [{"question_id": int, "answer": str}, ...] in the order of ``questions`` — the reference's result format.
     ``timings`` (dict, optional): receives the seconds spent in ``vit`` / ``kv`` / ``encoder`` / ``answer``
     (video_retrieval.phase_timer: HIP events, each phase synchronised).
@@ -101,6 +119,8 @@ def evaluation(model, videos, questions, question_ids, video_of_question, *, ans
     Q = len(questions)
     if Q == 0 or len(question_ids) != Q or voq.numel() != Q:
         raise ValueError(f"evaluation: {Q} questions, {len(question_ids)} question_ids and {voq.numel()} entries of video_of_question")
+    if map_with is not None and (inference != "generate" or answer_list is None):
+        raise ValueError("evaluation: map_with maps GENERATED answers onto answer_list (inference='generate' and answer_list)")
     if inference == "rank":
         if answer_list is None:
             raise ValueError("evaluation: inference='rank' needs answer_list")
@@ -158,5 +178,7 @@ def evaluation(model, videos, questions, question_ids, video_of_question, *, ans
                   for qid, row in zip(question_ids, out_tok.tolist())]
         if details is not None:
             details.update(tokens=out_tok)
+        if map_with is not None:
+            result = map_answers(result, answer_list, map_with)
     lap("answer", t0)
     return result
