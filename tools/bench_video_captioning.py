@@ -25,7 +25,7 @@ from vidil_amd import video_captioning as VC  # noqa: E402
 from vidil_amd.blip import BLIP_Video_Decoder  # noqa: E402
 from vidil_amd.packing import set_compute_dtype  # noqa: E402
 from vidil_amd.tokenizer import SyntheticBertTokenizer  # noqa: E402
-from vidil_amd.video_retrieval import phase_timer  # noqa: E402
+from vidil_amd.video import phase_timer  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--videos", type=int, default=256)

@@ -10,7 +10,7 @@ questions about each (in a shuffled order), an answer list of ``--answers``, ``i
 
 Every schedule runs twice after a warm-up through the kernel forms of the timed runs: once whole between two HIP events
 (``total_s``, ``questions_per_s``), once phase by phase, each phase between HIP events and synchronised (``vit_s``,
-``kv_s``, ``encoder_s``, ``stage1_s``, ``stage2_s``; ``video_retrieval.phase_timer`` throughout).
+``kv_s``, ``encoder_s``, ``stage1_s``, ``stage2_s``; ``video.phase_timer`` throughout).
 stage 1 is ``first_token_logprobs`` + ``topk_rows`` timed on its own; stage 2 is ``rank_answer`` minus that.  One JSON line.
 
 usage: python tools/bench_video_qa.py [--videos 256] [--frames 8] [--size 224] [--per-video 24] [--answers 1500] [--k-test 64]
@@ -32,7 +32,7 @@ from vidil_amd import video_qa as VQ  # noqa: E402
 from vidil_amd.blip_vqa import BLIP_Video_VQA  # noqa: E402
 from vidil_amd.packing import set_compute_dtype  # noqa: E402
 from vidil_amd.tokenizer import SyntheticBertTokenizer  # noqa: E402
-from vidil_amd.video_retrieval import default_videos_per_block, phase_timer  # noqa: E402
+from vidil_amd.video import phase_timer, videos_per_block  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--videos", type=int, default=256)
@@ -69,7 +69,7 @@ keys = args.frames * ((args.size // 16) ** 2 + 1)
 
 
 class Phases(dict):
-    """with phases("name"): ... adds the HIP-event seconds of the block (video_retrieval.phase_timer: synchronised at its end)."""
+    """with phases("name"): ... adds the HIP-event seconds of the block (video.phase_timer: synchronised at its end)."""
 
     def __call__(self, name):
         lap = phase_timer(self)
@@ -181,7 +181,7 @@ prop = torch.cuda.get_device_properties(0)
 line = dict(bench="video_qa_evaluation", videos=V, frames=args.frames, size=args.size, keys_per_video=keys, questions=Q,
             questions_per_video=args.per_video, answers=args.answers, k_test=args.k_test, dtype="bf16", weights="random-init",
             longest_question_tokens=int(model.tokenize_questions(questions)[0].shape[1]),
-            videos_per_block=int(default_videos_per_block(model, keys)),
+            videos_per_block=int(videos_per_block(model.text_encoder.config, keys)),
             shared=report(t_shared, Q, ph_shared), reference_call_shape=dict(batch=REF_BATCH, **report(t_ref, n_ref, ph_ref)),
             shared_over_reference_questions_per_s=round((Q / t_shared) / (n_ref / t_ref), 3), same_answers_share=round(same, 4),
             box=dict(device=prop.name, compute_units=prop.multi_processor_count, hip=torch.version.hip, torch=torch.__version__),

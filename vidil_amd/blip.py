@@ -16,18 +16,16 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
+from . import video as V
 from .med import BeamArena, BertConfig, BertLMHeadModel, CrossKV
-from .packing import FP8, compute_dtype, parity_mode, require_cuda
+from .packing import require_cuda
 from .tokenizer import init_tokenizer, refuse_synthetic_with_checkpoint  # noqa: F401  (init_tokenizer re-exported, reference API)
+from .video import CLIP_MEAN, CLIP_STD, MAX_VIDEO_TOKENS  # noqa: F401  (their home is video.py; imported from here too)
 from .vit import VisionTransformer, interpolate_pos_embed
 
 _DEFAULT_MED_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs", "med_config.json")
 
-CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)   # run_video_CapFilt.py:133
-CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 CAPTION_MAX_LENGTH = 40                           # models/blip.py:109 (captions given to forward are cut to 40 tokens)
-MAX_VIDEO_TOKENS = 16384                          # keys of vidil_attention's long-key and key-split forms: N frames x T tokens
-VIT_VIDEOS = 16                                   # videos per ViT pass of BLIP_Video_Decoder (video_qa.VIT_VIDEOS)
 
 
 def resolve_med_config(path):
@@ -612,46 +610,21 @@ class BLIP_Video_Decoder(BLIP_Decoder):
 
     # ------------------------------------------------------------------ refusals, by name, before anything is launched
     def _require_plain(self):
-        for m in self.modules():
-            if parity_mode(m):
-                raise ValueError("BLIP_Video_Decoder: the parity precision mode is not built for video captioning (the attention "
-                                 "forms past 768 keys have no error-compensated form) — set_parity_mode(False, model)")
-            if compute_dtype(m) == FP8:
-                raise ValueError("BLIP_Video_Decoder: fp8 is not built for video captioning — set_compute_dtype('f16' or 'bf16', model)")
+        V.require_plain(self, "BLIP_Video_Decoder", "video captioning", "the attention forms past 768 keys have no error-compensated form")
 
     def _require_video_tokens(self, n_tokens):
-        if n_tokens > MAX_VIDEO_TOKENS:
-            raise ValueError(f"BLIP_Video_Decoder: {n_tokens} tokens per video (frames x tokens per frame) exceed the {MAX_VIDEO_TOKENS} "
-                             f"keys the attention kernels serve — sample fewer frames or build the model with a smaller image_size")
+        V.require_video_tokens(n_tokens, "BLIP_Video_Decoder")
 
     # ------------------------------------------------------------------ frames -> tokens
-    @torch.no_grad()
     def video_tokens(self, video):
-        """f32 [B,N,3,S,S] (normalised) -> 16-bit [B*N*T, width]: the ViT over the B*N frames, VIT_VIDEOS videos per pass; a video's
-        N*T rows are contiguous."""
-        if video.dim() != 5 or video.shape[2] != 3:
-            raise ValueError(f"BLIP_Video_Decoder: f32 [B,N,3,S,S] expected, got {tuple(video.shape)}")
-        B, N = video.shape[:2]
-        self._require_video_tokens(N * (self.visual_encoder.patch_embed.num_patches + 1))
+        """f32 [B,N,3,S,S] (normalised) -> 16-bit [B*N*T, width] (video.frame_tokens), video.VIT_VIDEOS videos per ViT pass."""
         self._require_plain()
-        require_cuda(video, "BLIP_Video_Decoder.video_tokens")
-        parts = [self.visual_encoder.forward_both(video[b0:b0 + VIT_VIDEOS].reshape(-1, *video.shape[2:]))[1]
-                 for b0 in range(0, B, VIT_VIDEOS)]
-        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+        return V.frame_tokens(self.visual_encoder, video, who="BLIP_Video_Decoder.video_tokens", u8=False, videos_per_pass=V.VIT_VIDEOS)
 
-    @torch.no_grad()
     def video_tokens_u8(self, frames_u8):
-        """uint8 [B,N,S,S,3] frames (already S x S) -> the same, with /255 and the normalisation fused into the patch kernel
-        (BLIP_Video_VQA.video_tokens_u8's preprocessing)."""
-        if frames_u8.dim() != 5 or frames_u8.shape[-1] != 3 or frames_u8.dtype != torch.uint8:
-            raise ValueError(f"BLIP_Video_Decoder: uint8 [B,N,S,S,3] expected, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
-        B, N = frames_u8.shape[:2]
-        self._require_video_tokens(N * (self.visual_encoder.patch_embed.num_patches + 1))
+        """uint8 [B,N,S,S,3] frames (already S x S) -> the same, with /255 and the normalisation fused into the patch kernel."""
         self._require_plain()
-        require_cuda(frames_u8, "BLIP_Video_Decoder.video_tokens_u8")
-        parts = [self.visual_encoder.forward_u8(frames_u8[b0:b0 + VIT_VIDEOS].reshape(-1, *frames_u8.shape[2:]), CLIP_MEAN, CLIP_STD)[1]
-                 for b0 in range(0, B, VIT_VIDEOS)]
-        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+        return V.frame_tokens(self.visual_encoder, frames_u8, who="BLIP_Video_Decoder.video_tokens_u8", u8=True, videos_per_pass=V.VIT_VIDEOS)
 
     def _tokens(self, video):
         """(16-bit tokens [B*Te, width], B) of f32 [B,N,3,S,S] / uint8 [B,N,S,S,3] frames, or of token rows [B, Te, width]."""
@@ -663,17 +636,12 @@ class BLIP_Video_Decoder(BLIP_Decoder):
 
     # ------------------------------------------------------------------ searches over N*T keys per video
     def videos_per_block(self, tokens_per_video):
-        """Videos searched side by side by ``generate``: what video_retrieval.KV_BLOCK_BYTES holds of cross K / V (layers x 2 x
-        N*T x width x 2 bytes per video), at least 1 — video_retrieval.default_videos_per_block for this model's decoder."""
-        from .video_retrieval import KV_BLOCK_BYTES
-        cfg = self.text_decoder.config
-        return max(1, KV_BLOCK_BYTES // (cfg.num_hidden_layers * 2 * tokens_per_video * cfg.hidden_size * 2))
+        """Videos searched side by side by ``generate``: what video.KV_BLOCK_BYTES holds of this decoder's cross K / V."""
+        return V.videos_per_block(self.text_decoder.config, tokens_per_video)
 
     def _check_tokens(self, enc16, B):
         self._require_plain()
-        if B <= 0 or enc16.shape[0] % B:
-            raise ValueError(f"BLIP_Video_Decoder: {enc16.shape[0]} token rows do not divide into B={B} videos")
-        self._require_video_tokens(enc16.shape[0] // B)
+        V.video_rows(enc16, B, "BLIP_Video_Decoder")
 
     @torch.no_grad()
     def generate_ids(self, enc16, B, **kw):

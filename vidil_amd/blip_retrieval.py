@@ -26,6 +26,7 @@ from .blip import CLIP_MEAN, CLIP_STD, load_checkpoint
 from .blip_itm import ITM_MAX_LENGTH, BLIP_ITM
 from .packing import require_cuda
 from .tokenizer import refuse_synthetic_with_checkpoint
+from .video import frame_tokens
 
 
 class BLIP_Retrieval(BLIP_ITM):
@@ -83,9 +84,8 @@ class BLIP_Retrieval(BLIP_ITM):
         require_cuda(frames_u8, "BLIP_Retrieval.video_features_u8")
         if frames_u8.dim() != 5 or frames_u8.shape[-1] != 3:
             raise K.VidilHipError(f"video_features_u8: uint8 [B,N,S,S,3] expected, got {tuple(frames_u8.shape)}")
-        B, N = frames_u8.shape[:2]
-        _, y16 = self.visual_encoder.forward_u8(frames_u8.reshape(B * N, *frames_u8.shape[2:]), CLIP_MEAN, CLIP_STD)
-        return y16, self._video_embeds(y16, B, N)
+        y16 = frame_tokens(self.visual_encoder, frames_u8, who=None, u8=True)
+        return y16, self._video_embeds(y16, *frames_u8.shape[:2])
 
     @torch.no_grad()
     def video_features(self, video):
@@ -93,9 +93,8 @@ class BLIP_Retrieval(BLIP_ITM):
         require_cuda(video, "BLIP_Retrieval.video_features")
         if video.dim() != 5 or video.shape[2] != 3:
             raise K.VidilHipError(f"video_features: f32 [B,N,3,S,S] expected, got {tuple(video.shape)}")
-        B, N = video.shape[:2]
-        _, y16 = self.visual_encoder.forward_both(video.reshape(B * N, *video.shape[2:]))
-        return y16, self._video_embeds(y16, B, N)
+        y16 = frame_tokens(self.visual_encoder, video, who=None, u8=False)
+        return y16, self._video_embeds(y16, *video.shape[:2])
 
     @torch.no_grad()
     def text_features(self, texts, device, batch=512):

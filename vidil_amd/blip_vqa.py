@@ -34,17 +34,17 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .blip import CLIP_MEAN, CLIP_STD, BLIP_Decoder, create_vit, load_checkpoint, resolve_med_config
+from . import video as V
+from .blip import BLIP_Decoder, create_vit, load_checkpoint, resolve_med_config
 from .med import BertConfig, BertLMHeadModel, BertModel
-from .packing import FP8, compute_dtype, fp8_companion, parity_mode, require_cuda, set_compute_dtype, set_parity_mode
+from .packing import FP8, compute_dtype, fp8_companion, require_cuda, set_compute_dtype, set_parity_mode
 from .tokenizer import init_tokenizer, refuse_synthetic_with_checkpoint
-from .video_retrieval import default_videos_per_block, phase_timer
+from .video import MAX_VIDEO_TOKENS  # noqa: F401  (its home is video.py; imported from here too)
 
 VQA_QUESTION_MAX_LENGTH = 35     # models/blip_vqa.py:42
 VQA_NUM_BEAMS, VQA_MAX_LENGTH, VQA_MIN_LENGTH = 3, 10, 1    # models/blip_vqa.py:92,100-102
 VQA_LABEL_SMOOTHING = 0.1        # models/med.py:916 (the loss `rank_answer` negates)
 MAX_IMAGE_TOKENS = 768           # keys the attention kernels serve (vidil_attention: Nk <= 768): ViT-B/16 up to 432 px
-MAX_VIDEO_TOKENS = 16384         # keys of the long-key form (vidil_attention: Nk <= 16384): a video's N frames x T tokens
 
 
 class BLIP_VQA(nn.Module):
@@ -72,12 +72,7 @@ class BLIP_VQA(nn.Module):
 
     # ------------------------------------------------------------------ precision
     def _require_plain(self):
-        for m in self.modules():
-            if parity_mode(m):
-                raise ValueError("BLIP_VQA: the parity precision mode is not built for question answering (masked cross-attention "
-                                 "has no error-compensated form) — set_parity_mode(False, model)")
-            if compute_dtype(m) == FP8:
-                raise ValueError("BLIP_VQA: fp8 is not built for question answering — set_compute_dtype('f16' or 'bf16', model)")
+        V.require_plain(self, "BLIP_VQA", "question answering", "masked cross-attention has no error-compensated form")
 
     def _require_image_tokens(self, n_tokens=None):
         """The ViT's self-attention and the text encoder's cross-attention run over all image tokens, and the attention
@@ -186,6 +181,19 @@ class BLIP_VQA(nn.Module):
                                       label_smoothing=VQA_LABEL_SMOOTHING, prompt_length=1, cross_kv_len=q_lens)
         return res.loss_sum
 
+    def _answer(self, states16, Q, lens, answer, n, weights, train, inference, k_test):
+        """What ``forward`` does behind the question states (models/blip_vqa.py:46-116; BLIP_Video_VQA: :208-280)."""
+        if train:
+            a_ids, a_lens = self.tokenize_answers(answer)
+            loss = self.answer_loss(states16, Q, lens, a_ids, a_lens, n)
+            w = torch.as_tensor(weights, dtype=torch.float32).to(loss.device).view(-1)
+            return ((w.double() * loss.double()).sum() / Q).float()
+        if inference == "generate":
+            out_tok, _ = self.generate_answer_ids(states16, Q)
+            return [self.tokenizer.decode(row, skip_special_tokens=True) for row in out_tok.cpu().tolist()]
+        a_ids, a_lens = self.tokenize_answers(answer)
+        return self.rank_answer(states16, Q, lens, a_ids, a_lens, k_test)[0]
+
     @torch.no_grad()
     def forward(self, image, question, answer=None, n=None, weights=None, train=True, inference="rank", k_test=128):
         """Reference: models/blip_vqa.py:37-116.  image f32 [Q,3,S,S] on the GPU, one per question.
@@ -202,16 +210,7 @@ class BLIP_VQA(nn.Module):
         if ids.shape[0] != Q:
             raise ValueError(f"BLIP_VQA: {ids.shape[0]} questions for {Q} images")
         _, states16 = self.question_states(y16, Q, ids, lens)
-        if train:
-            a_ids, a_lens = self.tokenize_answers(answer)
-            loss = self.answer_loss(states16, Q, lens, a_ids, a_lens, n)
-            w = torch.as_tensor(weights, dtype=torch.float32).to(loss.device).view(-1)
-            return ((w.double() * loss.double()).sum() / Q).float()
-        if inference == "generate":
-            out_tok, _ = self.generate_answer_ids(states16, Q)
-            return [self.tokenizer.decode(row, skip_special_tokens=True) for row in out_tok.cpu().tolist()]
-        a_ids, a_lens = self.tokenize_answers(answer)
-        return self.rank_answer(states16, Q, lens, a_ids, a_lens, k_test)[0]
+        return self._answer(states16, Q, lens, answer, n, weights, train, inference, k_test)
 
 
 def blip_vqa(pretrained="", **kwargs):
@@ -233,16 +232,11 @@ def video_major_order(video_of_question, n_videos):
     [n_videos+1] — the sorted questions of video v are group_start[v] .. group_start[v+1]-1 (empty for a video nobody asks
     about); ``max_group`` — its largest gap."""
     v = torch.as_tensor(video_of_question).cpu().long().view(-1)
-    if v.numel() and not (0 <= int(v.min()) and int(v.max()) < n_videos):
-        raise ValueError(f"video_of_question must hold indices in [0, {n_videos})")
+    group_start, max_group = V.group_table(v, n_videos, "video_of_question")
     order = torch.argsort(v, stable=True)
     inverse = torch.empty_like(order)
     inverse[order] = torch.arange(v.numel())
-    group_start = torch.zeros(n_videos + 1, dtype=torch.int64)
-    group_start[1:] = torch.cumsum(torch.bincount(v, minlength=n_videos), 0)
-    gaps = group_start[1:] - group_start[:-1]
-    return dict(order=order, inverse=inverse, group_start=group_start.to(torch.int32),
-                max_group=int(gaps.max()) if n_videos else 0)
+    return dict(order=order, inverse=inverse, group_start=group_start, max_group=max_group)
 
 
 class BLIP_Video_VQA(BLIP_VQA):
@@ -250,38 +244,20 @@ class BLIP_Video_VQA(BLIP_VQA):
     a BLIP_VQA checkpoint loads as it does there."""
 
     def _require_video_tokens(self, n_tokens):
-        """A video's frames are ONE encoder sequence for the text encoder's cross-attention, and the long-key form of the
-        attention kernels serves at most MAX_VIDEO_TOKENS keys: refuse more here, by name, before anything is launched."""
-        if n_tokens > MAX_VIDEO_TOKENS:
-            raise ValueError(f"BLIP_Video_VQA: {n_tokens} tokens per video (frames x tokens per frame) exceed the {MAX_VIDEO_TOKENS} "
-                             f"keys the attention kernels serve — sample fewer frames or build the model with a smaller image_size")
+        V.require_video_tokens(n_tokens, "BLIP_Video_VQA")
 
     # ------------------------------------------------------------------ frames -> tokens
-    @torch.no_grad()
     def video_tokens(self, video):
-        """f32 [B,N,3,S,S] (normalised) -> 16-bit [B*N*T, width]: the ViT over the B*N frames.  A video's N*T rows are
-        contiguous — as encoder states it is ONE unit of N*T tokens (models/blip_vqa.py:198-201), no copy."""
-        if video.dim() != 5 or video.shape[2] != 3:
-            raise ValueError(f"BLIP_Video_VQA: f32 [B,N,3,S,S] expected, got {tuple(video.shape)}")
-        B, N = video.shape[:2]
+        """f32 [B,N,3,S,S] (normalised) -> 16-bit [B*N*T, width]: one ViT pass (video.frame_tokens; models/blip_vqa.py:198-201)."""
         self._require_image_tokens()
-        self._require_video_tokens(N * (self.visual_encoder.patch_embed.num_patches + 1))
-        require_cuda(video, "BLIP_Video_VQA.video_tokens")
         self._require_plain()
-        return self.visual_encoder.forward_both(video.reshape(B * N, *video.shape[2:]))[1]
+        return V.frame_tokens(self.visual_encoder, video, who="BLIP_Video_VQA.video_tokens", u8=False)
 
-    @torch.no_grad()
     def video_tokens_u8(self, frames_u8):
-        """uint8 [B,N,S,S,3] frames (already S x S) -> the same, with /255 and the normalisation fused into the patch kernel
-        (BLIP_Retrieval.video_features_u8's preprocessing)."""
-        if frames_u8.dim() != 5 or frames_u8.shape[-1] != 3 or frames_u8.dtype != torch.uint8:
-            raise ValueError(f"BLIP_Video_VQA: uint8 [B,N,S,S,3] expected, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
-        B, N = frames_u8.shape[:2]
+        """uint8 [B,N,S,S,3] frames (already S x S) -> the same, with /255 and the normalisation fused into the patch kernel."""
         self._require_image_tokens()
-        self._require_video_tokens(N * (self.visual_encoder.patch_embed.num_patches + 1))
-        require_cuda(frames_u8, "BLIP_Video_VQA.video_tokens_u8")
         self._require_plain()
-        return self.visual_encoder.forward_u8(frames_u8.reshape(B * N, *frames_u8.shape[2:]), CLIP_MEAN, CLIP_STD)[1]
+        return V.frame_tokens(self.visual_encoder, frames_u8, who="BLIP_Video_VQA.video_tokens_u8", u8=True)
 
     # ------------------------------------------------------------------ question states, a video shared by its questions
     @torch.no_grad()
@@ -291,7 +267,7 @@ class BLIP_Video_VQA(BLIP_VQA):
         int [Q].  Returns (h32, h16) [Q*Tq, C] in the caller's order: every position's last hidden state (pad positions too).
 
         The questions are sorted video-major (``video_major_order``) and the videos walked in blocks of ``videos_per_block``
-        (default: what fits video_retrieval.KV_BLOCK_BYTES): a block's cross-attention K / V are projected ONCE per video and
+        (default: what fits video.KV_BLOCK_BYTES): a block's cross-attention K / V are projected ONCE per video and
         the text encoder runs over the block's questions with the ``group_start`` table, so one staging of a video's K / V
         serves all its questions; a video without a question is an empty group.  Every block is launched with the same Tq
         (ids' width: the longest question of the call) and the same ``max_group`` bound — the largest group of the call,
@@ -301,13 +277,10 @@ class BLIP_Video_VQA(BLIP_VQA):
         ``f32=False``: the f32 copy of the states is not assembled and None is returned in its place (the answer decoder reads
         the 16-bit rows only).  The blocks' rows are joined by one copy (none when the call is one block) and put into the
         caller's order by one ``index_select`` (none when the questions arrive video-major).
-        ``timings`` (dict, optional): receives the seconds spent in ``kv`` / ``encoder`` (video_retrieval.phase_timer)."""
+        ``timings`` (dict, optional): receives the seconds spent in ``kv`` / ``encoder`` (video.phase_timer)."""
         require_cuda(tokens16, "BLIP_Video_VQA")
         self._require_plain()
-        if B <= 0 or tokens16.shape[0] % B:
-            raise ValueError(f"BLIP_Video_VQA: {tokens16.shape[0]} token rows do not divide into B={B} videos")
-        Te = tokens16.shape[0] // B
-        self._require_video_tokens(Te)
+        Te = V.video_rows(tokens16, B, "BLIP_Video_VQA")
         Q, Tq = ids.shape
         sched = video_major_order(video_of_question, B)
         if sched["order"].numel() != Q or lens.numel() != Q:
@@ -315,26 +288,21 @@ class BLIP_Video_VQA(BLIP_VQA):
                              f"video_of_question")
         te, dev = self.text_encoder, tokens16.device
         C = te.config.hidden_size
-        order, gs = sched["order"], sched["group_start"].long()
+        order = sched["order"]
         max_group = max(sched["max_group"], -(-33 // Tq))
         ids_s = ids.cpu()[order].to(torch.int32).to(dev).contiguous()
         lens_s = lens.cpu()[order].to(torch.int32).to(dev).contiguous()
         parts32, parts16 = [], []
         if videos_per_block is None:
-            videos_per_block = default_videos_per_block(self, Te)
+            videos_per_block = V.videos_per_block(te.config, Te)
         if videos_per_block < 1:
             raise ValueError(f"BLIP_Video_VQA: videos_per_block={videos_per_block}")
-        lap = phase_timer(timings)
-        for b0 in range(0, B, videos_per_block):
-            b1 = min(B, b0 + videos_per_block)
-            p0, p1 = int(gs[b0]), int(gs[b1])
-            if p1 == p0:
-                continue
+        lap = V.phase_timer(timings)
+        for b0, b1, p0, p1, groups in V.blocks(sched["group_start"], B, videos_per_block):
             t0 = lap()
             cross = te.project_cross_kv(tokens16[b0 * Te:b1 * Te], b1 - b0, Te, v_rowmajor=True)
             t0 = lap("kv", t0)
-            a32, a16 = te.encode(ids_s[p0:p1], lens_s[p0:p1], cross,
-                                 cross_groups=(gs[b0:b1 + 1] - p0).to(torch.int32).to(dev).contiguous(), cross_max_group=max_group)
+            a32, a16 = te.encode(ids_s[p0:p1], lens_s[p0:p1], cross, cross_groups=groups.to(dev).contiguous(), cross_max_group=max_group)
             if f32:
                 parts32.append(a32)
             parts16.append(a16)
@@ -348,19 +316,6 @@ class BLIP_Video_VQA(BLIP_VQA):
         return (joined(parts32) if f32 else None), joined(parts16)
 
     # ------------------------------------------------------------------ the reference's call
-    def _answer(self, states16, Q, lens, answer, n, weights, train, inference, k_test):
-        """What BLIP_VQA.forward does behind the question states (models/blip_vqa.py:208-280)."""
-        if train:
-            a_ids, a_lens = self.tokenize_answers(answer)
-            loss = self.answer_loss(states16, Q, lens, a_ids, a_lens, n)
-            w = torch.as_tensor(weights, dtype=torch.float32).to(loss.device).view(-1)
-            return ((w.double() * loss.double()).sum() / Q).float()
-        if inference == "generate":
-            out_tok, _ = self.generate_answer_ids(states16, Q)
-            return [self.tokenizer.decode(row, skip_special_tokens=True) for row in out_tok.cpu().tolist()]
-        a_ids, a_lens = self.tokenize_answers(answer)
-        return self.rank_answer(states16, Q, lens, a_ids, a_lens, k_test)[0]
-
     @torch.no_grad()
     def forward(self, video, question, answer=None, n=None, weights=None, train=True, inference="rank", k_test=128):
         """Reference: models/blip_vqa.py:196-280.  video f32 [B,N,3,S,S] on the GPU, one question per video.

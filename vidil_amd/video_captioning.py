@@ -3,7 +3,7 @@
 
 ``video_representation: concat_frame`` hands a batch's videos to ``BLIP_Video_Decoder.generate``: the ViT over the B*N frames,
 then a beam search per video over its N*T frame tokens as ONE encoder sequence, ``videos_per_block`` videos side by side
-(default: what ``video_retrieval.KV_BLOCK_BYTES`` holds of cross K / V).  ``single_frame`` captions frame int(N/2) alone through
+(default: what ``video.KV_BLOCK_BYTES`` holds of cross K / V).  ``single_frame`` captions frame int(N/2) alone through
 ``BLIP_Decoder``'s path (:88-91).  A video's caption does not depend on the batch or the block it falls in.
 
 Plain f16 / bf16 operands (the model refuses the parity precision mode and fp8)."""
@@ -11,8 +11,8 @@ from __future__ import annotations
 
 import torch
 
-from .blip import CLIP_MEAN, CLIP_STD, BLIP_Decoder
-from .video_retrieval import phase_timer
+from .blip import BLIP_Decoder
+from .video import frame_tokens, middle_frame, phase_timer
 
 
 @torch.no_grad()
@@ -21,7 +21,7 @@ def evaluation(model, batches, config, *, videos_per_block=None, timings=None, d
     — videos f32 [b,N,3,S,S] (normalised) or uint8 [b,N,S,S,3] (the fused preprocessing), numpy or torch, on any device;
     ``config``: ``video_representation`` (concat_frame | single_frame), ``num_beams``, ``max_length``, ``min_length`` — the keys
     the reference's loop reads.  Returns [{"video_id": ..., "caption": str}, ...] in the order the videos arrive.
-    ``timings`` (dict, optional): receives the seconds spent in ``vit`` / ``search`` (video_retrieval.phase_timer: HIP events,
+    ``timings`` (dict, optional): receives the seconds spent in ``vit`` / ``search`` (video.phase_timer: HIP events,
     each phase synchronised; the search includes the cross K | V projection).  ``details`` (dict, optional; what the tests
     compare): receives ``tokens``, the i32 [videos, max_length] token ids of the captions, on the host."""
     rep = config["video_representation"]
@@ -39,7 +39,7 @@ def evaluation(model, batches, config, *, videos_per_block=None, timings=None, d
             raise ValueError(f"evaluation: a batch of [b,N,3,S,S] (f32) or [b,N,S,S,3] (uint8) videos with b video_ids expected, got "
                              f"{tuple(videos.shape)} and {len(video_ids)} ids")
         if rep == "single_frame":
-            videos = videos[:, int(videos.shape[1] / 2)]                 # pick middle frame (:89-91)
+            videos = middle_frame(videos)                                # pick middle frame (:89-91)
         videos = videos.to(dev)
         t0 = lap()
         if rep == "concat_frame":
@@ -50,10 +50,7 @@ def evaluation(model, batches, config, *, videos_per_block=None, timings=None, d
                                       details=det, **kw)
             out_tok = det["tokens"]
         else:
-            if videos.dtype == torch.uint8:
-                tok16 = model.visual_encoder.forward_u8(videos, CLIP_MEAN, CLIP_STD)[1]
-            else:
-                tok16 = model.visual_encoder.forward_both(videos)[1]
+            tok16 = frame_tokens(model.visual_encoder, videos, who=None)  # (its own check above; BLIP_Decoder refuses the rest)
             t0 = lap("vit", t0)
             out_tok = BLIP_Decoder.generate_ids(model, tok16, videos.shape[0], **kw)[0].cpu()
             captions = model.decode_captions(out_tok)

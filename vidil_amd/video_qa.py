@@ -10,7 +10,7 @@ MSRVTT-QA.  Schedule of ``evaluation``:
   * the ViT runs once per video, batch by batch of ``videos``; the tokens of all videos stay on the device (N*T x width x 2
     bytes per video: 2.4 MB at 224^2 x 8 frames), the frames themselves are consumed batch by batch;
   * ``BLIP_Video_VQA.question_states_grouped``: the questions sorted video-major, the videos walked in blocks of
-    ``videos_per_block`` (default: what fits ``video_retrieval.KV_BLOCK_BYTES``), a block's cross-attention K / V projected
+    ``videos_per_block`` (default: what fits ``video.KV_BLOCK_BYTES``), a block's cross-attention K / V projected
     once per video, the text encoder over the block's questions with one staging of a video's K / V for all of them.  Every
     block runs with the token count of the call's longest question and the call's ``max_group``: a question's bits do not
     depend on the block size, nor on the order the caller lists the questions in;
@@ -26,12 +26,10 @@ import re
 
 import torch
 
-from .video_retrieval import phase_timer
+from .video import VIT_VIDEOS, middle_frame, phase_timer  # (VIT_VIDEOS: videos per ViT pass when ``videos`` is one tensor)
 
 #: questions per ``rank_answer`` / ``generate_answer_ids`` call of ``evaluation`` (bounds the [questions, vocabulary] f32 logits)
 RANK_QUESTIONS = 1024
-#: videos per ViT pass when ``videos`` is one tensor
-VIT_VIDEOS = 16
 
 
 # ---------------------------------------------------------------------------------------------- annotations
@@ -106,7 +104,7 @@ def evaluation(model, videos, questions, question_ids, video_of_question, *, ans
     mapped onto ``answer_list`` by ``map_answers`` — the result the reference's eval_video_qa_result.py scores.
     Returns [{"question_id": int, "answer": str}, ...] in the order of ``questions`` — the reference's result format.
     ``timings`` (dict, optional): receives the seconds spent in ``vit`` / ``kv`` / ``encoder`` / ``answer``
-    (video_retrieval.phase_timer: HIP events, each phase synchronised).
+    (video.phase_timer: HIP events, each phase synchronised).
     ``details`` (dict, optional; diagnostic output, what the tests compare — not part of the reference's interface): receives, on
     the host, ``max_ids`` int64 [Q], ``topk_ids`` i32 [Q, k_test] and ``log_probs_sum``
     f32 [Q, k_test] (rank) or ``tokens`` i32 [Q, 10] (generate)."""
@@ -142,8 +140,7 @@ def evaluation(model, videos, questions, question_ids, video_of_question, *, ans
         elif batch.shape[1] != n_frames:
             raise ValueError(f"evaluation: every video needs the same number of frames ({n_frames}), got {batch.shape[1]}")
         if video_representation == "single_frame":
-            mid = int(n_frames / 2)                                       # (train_vqa_video.py:85-86)
-            batch = batch[:, mid:mid + 1]
+            batch = middle_frame(batch)                                   # (train_vqa_video.py:85-86)
         batch = batch.to(dev)
         tokens.append(model.video_tokens_u8(batch) if batch.dtype == torch.uint8 else model.video_tokens(batch))
     if not tokens:

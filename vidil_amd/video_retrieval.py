@@ -18,7 +18,7 @@ Schedule of ``evaluation`` (the reference runs one text-encoder batch of k_test 
   * both score matrices are scattered from the one score vector ``itm_logit[:, 1] + sim``: a pair that is a candidate in
     both directions holds the same bits in both.
 
-``videos_per_block`` defaults to what fits ``KV_BLOCK_BYTES``: a video's K / V are L layers x 2 (K, V) x N*T keys x C
+``videos_per_block`` defaults to what fits ``video.KV_BLOCK_BYTES``: a video's K / V are L layers x 2 (K, V) x N*T keys x C
 channels x 2 bytes (12 x 2 x 1,576 x 768 x 2 B = 58 MB at 224^2 x 8 frames, 170 MB at 384^2 x 8).  The frames' tokens of
 all videos stay on the device (N*T x width x 2 bytes per video: 2.4 GB for 1,000 videos at 224^2 x 8 frames); the frames
 themselves are consumed batch by batch.
@@ -34,9 +34,9 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from . import video
+from .video import KV_BLOCK_BYTES, phase_timer  # noqa: F401  (their home is video.py; imported from here too)
 
-#: budget of one block's cross-attention K / V (see the module docstring)
-KV_BLOCK_BYTES = 4 << 30
 FILL = -100.0                      # eval_retrieval_video.py:77,100
 
 
@@ -81,11 +81,8 @@ def pair_union(idx_v2t, idx_t2v):
     keys, inv = torch.unique(torch.cat([key_v2t.reshape(-1), key_t2v.reshape(-1)]), sorted=True, return_inverse=True)
     pair_video = torch.div(keys, Tn, rounding_mode="floor") if Tn else keys
     pair_text = keys - pair_video * Tn
-    group_start = torch.zeros(V + 1, dtype=torch.int64)
-    group_start[1:] = torch.cumsum(torch.bincount(pair_video, minlength=V), 0)
-    gaps = group_start[1:] - group_start[:-1]
-    return dict(pair_video=pair_video, pair_text=pair_text, group_start=group_start.to(torch.int32),
-                max_group=int(gaps.max()) if V else 0,
+    group_start, max_group = video.group_table(pair_video, V)
+    return dict(pair_video=pair_video, pair_text=pair_text, group_start=group_start, max_group=max_group,
                 slot_v2t=inv[:key_v2t.numel()].view(idx_v2t.shape), slot_t2v=inv[key_v2t.numel():].view(idx_t2v.shape))
 
 
@@ -101,26 +98,8 @@ def scatter_scores(sched, pair_score, idx_v2t, idx_t2v, V, Tn):
 
 
 def default_videos_per_block(model, tokens_per_video):
-    """KV_BLOCK_BYTES // (L * 2 * N*T * C * 2 bytes), at least 1."""
-    cfg = model.text_encoder.config
-    per_video = cfg.num_hidden_layers * 2 * tokens_per_video * cfg.hidden_size * 2
-    return max(1, KV_BLOCK_BYTES // per_video)
-
-
-def phase_timer(timings):
-    """lap = phase_timer(timings): ``t0 = lap()`` marks a start on the current stream and ``lap(name, t0)`` adds the seconds
-    between that mark and now to timings[name] (HIP events, synchronised at the end of the phase) and returns a new mark.
-    With ``timings`` None nothing is recorded and nothing is synchronised."""
-    def lap(name=None, t0=None):
-        if timings is None:
-            return None
-        now = torch.cuda.Event(enable_timing=True)
-        now.record()
-        if name is not None:
-            now.synchronize()
-            timings[name] = timings.get(name, 0.0) + t0.elapsed_time(now) / 1e3
-        return now
-    return lap
+    """video.videos_per_block for the model's text encoder."""
+    return video.videos_per_block(model.text_encoder.config, tokens_per_video)
 
 
 # ---------------------------------------------------------------------------------------------- evaluation
@@ -168,16 +147,12 @@ def evaluation(model, videos, texts, k_test, *, videos_per_block=None, device="c
     _, idx_v2t = K.topk_rows(sims, min(k_test, Tn))                       # (:86)
     _, idx_t2v = K.topk_rows(sims.t().contiguous(), min(k_test, V))       # (:99,108)
     sched = pair_union(idx_v2t.cpu(), idx_t2v.cpu())
-    pv, pt, gs = sched["pair_video"], sched["pair_text"], sched["group_start"].long()
+    pv, pt = sched["pair_video"], sched["pair_text"]
     itm = torch.empty(pv.numel(), dtype=torch.float32, device=dev)
     t_eff = max(1, min(ids.shape[1], int(lens.max().item())))
     if videos_per_block is None:
         videos_per_block = default_videos_per_block(model, Te)
-    for b0 in range(0, V, videos_per_block):
-        b1 = min(V, b0 + videos_per_block)
-        p0, p1 = int(gs[b0]), int(gs[b1])
-        if p1 == p0:
-            continue
+    for b0, b1, p0, p1, groups in video.blocks(sched["group_start"], V, videos_per_block):
         t0 = time.perf_counter()
         enc = tokens[b0 * Te:b1 * Te]
         cross = model.project_image_kv(enc, b1 - b0, sched["max_group"] * t_eff)
@@ -186,8 +161,7 @@ def evaluation(model, videos, texts, k_test, *, videos_per_block=None, device="c
         uniq, local = torch.unique(pt[p0:p1], sorted=True, return_inverse=True)    # the block's distinct texts
         uniq = uniq.to(dev)
         out = model.itm_pairs(enc, b1 - b0, ids.index_select(0, uniq), lens.index_select(0, uniq),
-                              group_start=(gs[b0:b1 + 1] - p0).to(torch.int32), max_group=sched["max_group"],
-                              pair_text=local, cross=cross, t_eff=t_eff)
+                              group_start=groups, max_group=sched["max_group"], pair_text=local, cross=cross, t_eff=t_eff)
         itm[p0:p1] = out[:, 1]
         lap("pairs", t0)
     score = itm + sims[pv.to(dev), pt.to(dev)]                            # score + topk_sim (:97,118)
