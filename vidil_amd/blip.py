@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from . import kernels as K
 from . import video as V
-from .med import BeamArena, BertConfig, BertLMHeadModel, CrossKV
+from .med import BeamArena, BertConfig, BertLMHeadModel, BertModel, CrossKV
 from .packing import require_cuda
 from .tokenizer import init_tokenizer, refuse_synthetic_with_checkpoint  # noqa: F401  (init_tokenizer re-exported, reference API)
 from .video import CLIP_MEAN, CLIP_STD, MAX_VIDEO_TOKENS  # noqa: F401  (their home is video.py; imported from here too)
@@ -190,6 +190,52 @@ class DecoderSession:
                              arena=self.arena, fused=self.fused_ln)
         self.logits = self.dec.lm_logits(h16, self.R, 1, out=self.logits, h32=h32)
         return self.logits
+
+
+class BLIP_Base(nn.Module):
+    """The reference's feature extractor (models/blip.py:22-74): a ViT and the cross-attending text encoder, no heads."""
+
+    def __init__(self, med_config="configs/med_config.json", image_size=224, vit="base", vit_grad_ckpt=False, vit_ckpt_layer=0,
+                 tokenizer=None):
+        super().__init__()
+        self.visual_encoder, vision_width = create_vit(vit, image_size, vit_grad_ckpt, vit_ckpt_layer)
+        self.tokenizer = tokenizer if tokenizer is not None else init_tokenizer()
+        cfg = BertConfig.from_json_file(resolve_med_config(med_config))
+        cfg.encoder_width = vision_width
+        self.text_encoder = BertModel(config=cfg, add_pooling_layer=False)
+
+    @torch.no_grad()
+    def forward(self, image, caption, mode):
+        """models/blip.py:45-73.  image f32 [B,3,S,S] on the device, caption a string or B strings.
+        mode='image': the ViT's tokens f32 [B, T, width]; 'text': the text encoder's states without cross-attention, f32
+        [B, L, C]; 'multimodal': first id := [ENC], the states of the encoder cross-attending to the image's tokens.
+        Captions of different lengths are padded to the longest (L) and masked (``BertModel.forward``'s prefix-mask form) —
+        the reference tokenises without padding, which only works for equal lengths."""
+        assert mode in ["image", "text", "multimodal"], "mode parameter must be image, text, or multimodal"
+        require_cuda(image, "BLIP_Base.forward")
+        dev = image.device
+        if mode == "image":
+            return self.visual_encoder(image)
+        text = self.tokenizer([caption] if isinstance(caption, str) else list(caption), padding="longest", return_tensors="pt")
+        ids, mask = text.input_ids.clone(), text.attention_mask.to(dev)
+        if mode == "text":
+            return self.text_encoder(ids.to(dev), attention_mask=mask, return_dict=True, mode="text").last_hidden_state
+        B = image.shape[0]
+        _, y16 = self.visual_encoder.forward_both(image)
+        ids[:, 0] = self.tokenizer.enc_token_id
+        # (encoder_attention_mask: the reference's all-ones image_atts is the default)
+        return self.text_encoder(ids.to(dev), attention_mask=mask, encoder_hidden_states=y16.view(B, -1, y16.shape[-1]),
+                                 return_dict=True).last_hidden_state
+
+
+def blip_feature_extractor(pretrained="", **kwargs):
+    """Reference: models/blip.py:283-288."""
+    model = BLIP_Base(**kwargs)
+    if pretrained:
+        refuse_synthetic_with_checkpoint(model.tokenizer, pretrained)
+        model, msg = load_checkpoint(model, pretrained)
+        assert len(msg.missing_keys) == 0
+    return model
 
 
 class BLIP_Decoder(nn.Module):

@@ -88,14 +88,19 @@ class BLIP_ITM(PackedCache, nn.Module):
         """models/blip_itm.py:60-67 (match_head='itc'): normalize(vision_proj(image [CLS])) @ normalize(text_proj(text [CLS]))^T
         with the text encoder in mode='text' (no cross-attention) -> f32 [n_images, len(captions)], exact-f32 scores.
         y32: the ViT's f32 output — needed in the parity precision mode, whose projections take the f32 states."""
+        return K.scan_scores(*self.itc_features(y16, n_images, captions, device, y32=y32))
+
+    @torch.no_grad()
+    def itc_features(self, y16, n_images, captions, device, y32=None):
+        """The two operands of ``itc_similarity``: (unit-norm image embeddings f32 [n_images, embed_dim], unit-norm text
+        embeddings f32 [len(captions), embed_dim])."""
         if self.parity and y32 is None:
             raise ValueError("itc_similarity (parity mode): pass the ViT's f32 output as y32=")
         img = self.image_embeds(y32, y16, n_images)
         ids, lens = self.tokenize(list(captions))
         t_eff = max(1, min(ITM_MAX_LENGTH, int(lens.max().item())))
         d_ids = ids[:, :t_eff].to(device).contiguous()
-        txt = self.text_embeds(d_ids, lens.to(device).contiguous())
-        return K.scan_scores(img, txt)
+        return img, self.text_embeds(d_ids, lens.to(device).contiguous())
 
     # ------------------------------------------------------------------ tokenisation
     def tokenize(self, captions):

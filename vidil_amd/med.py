@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import kernels as K
 from .packing import FP8, PackedCache, fold_layernorm, parity_attention_arith, parity_attention_f32, parity_attention_kind, require_cuda, v32, w3, w8, w16
+from .video import MAX_VIDEO_TOKENS
 
 LN_EPS_DEFAULT = 1e-12
 
@@ -69,6 +70,20 @@ class CaptionScores:
         """Indices (int64, device) of caption p's target tokens, in position order."""
         idx = (self.caption == p).nonzero().view(-1)
         return idx[self.position[idx].argsort()]
+
+
+class ModelOutput:
+    """What the reference-signature ``forward``s return with return_dict=True: the fields as attributes and by name, and —
+    as the HF output classes — by position over the fields that are not None."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def to_tuple(self):
+        return tuple(v for v in self.__dict__.values() if v is not None)
+
+    def __getitem__(self, key):
+        return self.__dict__[key] if isinstance(key, str) else self.to_tuple()[key]
 
 
 class BertConfig:
@@ -212,8 +227,8 @@ class BeamArena:
 
 
 class BertModel(PackedCache, nn.Module):
-    """ITM text encoder / decoder trunk.  ``forward`` is not the generic HF signature: the hot
-    path calls ``encode`` (ITM) or is driven by ``BertLMHeadModel``."""
+    """ITM text encoder / decoder trunk.  The hot path calls ``encode`` (ITM) or is driven by ``BertLMHeadModel``;
+    ``forward`` takes the reference's call (the HF signature) and runs it on the same passes."""
 
     #: images per cross-attention / cross K|V projection launch of a decode batch (a search over more images — the images of
     #: several tower chunks — issues these launches per block of this many images: byte-floor kernels whose launch already fills
@@ -386,7 +401,7 @@ class BertModel(PackedCache, nn.Module):
     def run_layers(self, h32, h16, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len,
                    cross: CrossKV, cross_index=None, cross_group=1, cross_groups=None, cross_max_group=0, ws=None,
                    arena: "BeamArena" = None, arena_slot_stride=1, n_layers=None, self_done_first=False,
-                   stop_after_self=False, fused=None, cross_kv_len=None, arena_prompt=False):
+                   stop_after_self=False, fused=None, cross_kv_len=None, arena_prompt=False, hidden_out=None):
         """Run every layer on the f32/f16 hidden pair (both [rows*T, C], updated in place).
 
         self_k / self_vt: [L][rows,H,Tk_cap,64] / [L][rows,H,64,NPs] — this call's keys are appended at
@@ -402,6 +417,9 @@ class BertModel(PackedCache, nn.Module):
 
         cross_kv_len (i32 [rows], device; default None: every one of cross.Te keys): query batch r attends to the first
         cross_kv_len[r] keys of its encoder unit only (a decoder over padded question states: models/blip_vqa.py:69-76,125-129).
+
+        hidden_out (a list; BertModel.forward(output_hidden_states=True)): receives a f32 [rows*T, C] copy of the normalised
+        hidden states after every layer run.  Not built for the parity precision mode.
         """
         p = self.packed()
         cfg = self.config
@@ -410,6 +428,8 @@ class BertModel(PackedCache, nn.Module):
         M = rows * T
         dev = h32.device
         cdt = h16.dtype
+        if p["parity"] and hidden_out is not None:
+            raise K.VidilHipError("run_layers: hidden_out (per-layer hidden states) is not built for the parity precision mode")
         if p["parity"]:
             if self_done_first or stop_after_self or n_layers is not None:
                 raise K.VidilHipError("run_layers: the parity precision mode runs whole stacks (the caption decoder, "
@@ -437,7 +457,8 @@ class BertModel(PackedCache, nn.Module):
                                           NPs=NPs, causal=causal, kv_len=kv_len, cross=cross, cross_index=cross_index,
                                           cross_group=cross_group, cross_groups=cross_groups, cross_max_group=cross_max_group,
                                           n_layers=n_layers, self_done_first=self_done_first, arena=arena,
-                                          arena_slot_stride=arena_slot_stride, cross_kv_len=cross_kv_len, arena_prompt=arena_prompt)
+                                          arena_slot_stride=arena_slot_stride, cross_kv_len=cross_kv_len, arena_prompt=arena_prompt,
+                                          hidden_out=hidden_out)
         if ws is None:
             ws = {}
         q = ws.get("q")
@@ -492,6 +513,8 @@ class BertModel(PackedCache, nn.Module):
             K.gemm(h16, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
             K.gemm(inter, d["o_w"], d["o_b"], out=tmp, resid=h32)
             K.layernorm(tmp, d["o_g"], d["o_bt"], eps, out16=h16, out32=h32)
+            if hidden_out is not None:
+                hidden_out.append(h32.clone())
         return h32, h16
 
     #: vidil_attention's short kernels end here; past it the long-key form serves MORE than 32 query rows per unit on plain K / V,
@@ -684,7 +707,7 @@ class BertModel(PackedCache, nn.Module):
     def _run_layers_fused(self, h32, h16, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len, cross, cross_index=None,
                           cross_group=1, cross_groups=None, cross_max_group=0, n_layers=None, self_done_first=False,
                           stop_after_self=False, state_in=None, arena: "BeamArena" = None, arena_slot_stride=1, cross_kv_len=None,
-                          arena_prompt=False):
+                          arena_prompt=False, hidden_out=None):
         """run_layers for encoder batches with cross-attention, WITHOUT LayerNorm launches between the GEMMs
         (models/med.py:236-239,306-317 are post-LN: h = LN(x + dense(.)) is the next dense's input AND the next residual).
         The stream is kept as the RAW sums u (f32 in h32's storage, a 16-bit copy in h16's) plus per-row (sum, sum of
@@ -780,6 +803,10 @@ class BertModel(PackedCache, nn.Module):
             residual_gemm(o, d["co_w"], d["co_b"], d["co_g"], d["co_bt"])
             consumer("fc1", i, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
             residual_gemm(inter, d["o_w"], d["o_b"], d["o_g"], d["o_bt"])
+            if hidden_out is not None:   # (the stream is raw here: the layer's output LayerNorm into a buffer of its own)
+                snap = torch.empty_like(h32)
+                K.layernorm(h32, pend[0], pend[1], eps, out32=snap)
+                hidden_out.append(snap)
         if pend is not None:         # hand the caller normalised (h32, h16) again
             K.layernorm(h32, pend[0], pend[1], eps, out16=h16, out32=h32)
         return h32, h16
@@ -799,24 +826,50 @@ class BertModel(PackedCache, nn.Module):
         K.layernorm(raw, p["emb_g"], p["emb_b"], self.config.layer_norm_eps, out16=h16, out32=h32, split3=par)
         return h32, h16
 
-    def encode(self, ids_i32, kv_len_i32, cross: CrossKV, cross_index=None, cross_groups=None, cross_max_group=0):
+    def encode(self, ids_i32, kv_len_i32, cross: CrossKV, cross_index=None, cross_groups=None, cross_max_group=0, cross_kv_len=None):
         """ITM encoder pass (models/blip_itm.py:51-56): ids int32 [P,T] right-padded, kv_len [P] = number of
         real tokens.  Pair p attends to image ``cross_index[p]``, or — image-major pair order — image j serves
-        pairs cross_groups[j] .. cross_groups[j+1]-1.  Returns (h32, h16) [P*T, C]."""
+        pairs cross_groups[j] .. cross_groups[j+1]-1.  cross_kv_len (i32 [P], device): pair p attends to the first
+        cross_kv_len[p] encoder states of its unit only (run_layers).  Returns (h32, h16) [P*T, C]."""
         require_cuda(ids_i32, "BertModel.encode")
         P, T = ids_i32.shape
+        h32, h16 = self.embed(ids_i32.reshape(-1), T, 0)
+        return self.bidirectional_pass(h32, h16, P, T, kv_len_i32, cross, cross_index=cross_index, cross_groups=cross_groups,
+                                       cross_max_group=cross_max_group, cross_kv_len=cross_kv_len)
+
+    def bidirectional_pass(self, h32, h16, P, T, kv_len_i32, cross, *, hidden_out=None, **cross_kw):
+        """The stack pass of ``encode`` on embedded rows (h32, h16) [P*T, C], updated in place: every token attends to the first
+        kv_len[p] tokens of its sequence and to ``cross`` (cross_kw: cross_index / cross_groups / cross_max_group / cross_kv_len)."""
         H = self.config.num_attention_heads
         L = self.config.num_hidden_layers
-        dev = ids_i32.device
+        dev = h32.device
         NPs = (T + 15) // 16 * 16
-        h32, h16 = self.embed(ids_i32.reshape(-1), T, 0)
         cdt = h16.dtype
         sk = torch.empty((1, P, H, T, 64), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
         sv = torch.empty((1, P, H, 64, NPs), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
         # (one scratch K / V^T buffer is reused by every layer: the encoder keeps no cache)
         self.run_layers(h32, h16, rows=P, T=T, self_k=sk, self_vt=sv, t_off=0, Tk_cap=T, NPs=NPs, causal=False,
-                        kv_len=kv_len_i32, cross=cross, cross_index=cross_index, cross_groups=cross_groups,
-                        cross_max_group=cross_max_group)
+                        kv_len=kv_len_i32, cross=cross, hidden_out=hidden_out, **cross_kw)
+        return h32, h16
+
+    def causal_pass(self, h32, h16, rows, T, cross, *, kv_len=None, hidden_out=None, **cross_kw):
+        """The stack pass of ``BertLMHeadModel.score`` / ``start_logits`` on embedded rows (h32, h16) [rows*T, C], updated in
+        place: every block of T tokens attends causally to itself through one scratch K / V^T pair shared by all layers (as
+        DecoderSession.prefill does for a prompt) and to ``cross`` (cross_kw: cross_index / cross_groups / cross_max_group /
+        cross_kv_len).  The stack is the one a DecoderSession runs (LN-folded or parity) — never a function of the batch.
+        kv_len (i32 [rows], device): a row also ignores the keys past kv_len[r] (models/med.py:651, causal x padding mask);
+        a query inside its sequence sees the same keys with and without it."""
+        cfg = self.config
+        H, L = cfg.num_attention_heads, cfg.num_hidden_layers
+        dev = h32.device
+        cdt = h16.dtype
+        fused = (os.environ.get("VIDIL_DECODE_FUSE_LN", "1") != "0" and not self.parity and self._text_fold_ok(cdt)
+                 and cfg.add_cross_attention and cross is not None)
+        NPs = (T + 15) // 16 * 16
+        sk = torch.empty((1, rows, H, T, 64), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
+        sv = torch.empty((1, rows, H, 64, NPs), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
+        self.run_layers(h32, h16, rows=rows, T=T, self_k=sk, self_vt=sv, t_off=0, Tk_cap=T, NPs=NPs, causal=True, kv_len=kv_len,
+                        cross=cross, fused=fused, hidden_out=hidden_out, **cross_kw)
         return h32, h16
 
     def encode_cls(self, ids_i32, kv_len_i32, cross: CrossKV, cross_index=None, cross_groups=None, cross_max_group=0,
@@ -964,8 +1017,152 @@ class BertModel(PackedCache, nn.Module):
         K.layernorm(tmp, d["o_g"], d["o_bt"], eps, out16=c3, out32=c32, split3=True)
         return c32, c3
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("use BertModel.encode / BLIP_ITM on the hot path")
+    # ------------------------------------------------------------------ the reference's call surface
+    def masked_pass(self, h32, h16, B, T, keep=None, *, causal=False, cross=None, cross_kv_len=None, hidden_out=None):
+        """The stack on embedded rows (h32, h16) [B*T, C] under a 0/1 key mask ``keep`` (bool [B, T], device; None: all ones):
+        the rows with mask 1 are moved to the front of their sequence in their original order (attention does not depend on
+        the order of its keys, and the positions are already in the embedding), the stack runs with their count as ``kv_len``
+        (``bidirectional_pass``, or ``causal_pass`` — the stable order keeps the causal relation among the kept rows), and the
+        rows are moved back.  A mask whose ones form a prefix moves nothing: the launches and bits are those of ``encode`` /
+        ``causal_pass`` on the same lengths.  The permutation is computed on the device; nothing is read back.
+        Returns new (h32, h16); hidden_out receives the per-layer states in the caller's row order."""
+        if keep is None:
+            rows, kv_len = None, None
+        else:
+            order = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)          # kept rows first, original order
+            rows = (torch.arange(B, device=keep.device)[:, None] * T + order).reshape(-1)
+            kv_len = keep.sum(1).to(torch.int32).contiguous()
+            h32, h16 = h32.index_select(0, rows), h16.index_select(0, rows)
+        kw = {} if cross_kv_len is None else dict(cross_kv_len=cross_kv_len)
+        states = None if hidden_out is None else []
+        if causal:
+            self.causal_pass(h32, h16, B, T, cross, kv_len=kv_len, hidden_out=states, **kw)
+        else:
+            self.bidirectional_pass(h32, h16, B, T, kv_len, cross, hidden_out=states, **kw)
+        if rows is not None:
+            def back(x):
+                return torch.empty_like(x).index_copy_(0, rows, x)
+            h32, h16 = back(h32), back(h16)
+            states = None if states is None else [back(x) for x in states]
+        if states is not None:
+            hidden_out.extend(states)
+        return h32, h16
+
+    def _cross_for_forward(self, encoder_hidden_states, encoder_attention_mask, B, Tq):
+        """forward's cross-attention keys / values: encoder states [B, Te, width] (f32 or the 16-bit type) under a 0/1 mask
+        [B, Te] -> (CrossKV, cross_kv_len).  With a mask the kept rows of each unit are moved to its front before the K | V
+        projection and their count becomes cross_kv_len.  More than LONG_KEYS states: plain rows for more than 32 query rows
+        per unit (the long-key form), fragment tiles otherwise (the key-split form)."""
+        enc = encoder_hidden_states
+        Te, W = enc.shape[1], enc.shape[2]
+        enc16 = enc.to(self.cdt).reshape(B * Te, W)
+        ckl = None
+        if encoder_attention_mask is not None:
+            keep = encoder_attention_mask.to(enc.device) != 0
+            order = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)
+            rows = (torch.arange(B, device=enc.device)[:, None] * Te + order).reshape(-1)
+            enc16 = enc16.index_select(0, rows)
+            ckl = keep.sum(1).to(torch.int32).contiguous()
+        long_keys = Te > self.LONG_KEYS
+        kw = dict(tiled=True) if long_keys and Tq <= 32 else dict(v_rowmajor=Tq > 32)
+        return self.project_cross_kv(enc16.contiguous(), B, Te, kv_len=ckl, **kw), ckl
+
+    def _forward_states(self, name, input_ids, attention_mask, encoder_hidden_states, encoder_attention_mask, output_hidden_states,
+                        is_decoder, mode, refused):
+        """What both ``forward``s run: checks first (nothing is launched that would fail), then the embedding and ``masked_pass``.
+        Returns (h32, h16, Tp, last, hidden): h32 / h16 [B*Tp, C] are the states of B blocks of Tp >= T tokens (a causal call
+        runs on blocks of at least SCORE_MIN_TOKENS tokens, as ``BertLMHeadModel.score`` does; the added positions are padding);
+        ``last`` f32 [B, T, C] and ``hidden`` (a tuple of L + 1 such tensors, or None) are cut to the caller's T tokens."""
+        for arg, value in refused:
+            if value is not None and value is not False:
+                raise NotImplementedError(f"{name}: {arg}{'=True' if value is True else ''} is not served (BertModel.forward's "
+                                          "docstring lists what is)")
+        if isinstance(encoder_hidden_states, (list, tuple)):
+            raise NotImplementedError(f"{name}: a list as encoder_hidden_states (the NLVR encoder's call, models/med.py:748) is not served")
+        if mode not in ("text", "multimodal"):
+            raise NotImplementedError(f"{name}: mode={mode!r} is not served (text | multimodal)")
+        if input_ids is None:
+            raise ValueError(f"{name}: input_ids is required")
+        if self.parity:
+            raise NotImplementedError(f"{name}: the parity precision mode is not served (BertModel.encode / BertLMHeadModel.score are)")
+        require_cuda(input_ids, name)
+        if input_ids.dim() != 2 or input_ids.dtype not in (torch.int64, torch.int32):
+            raise ValueError(f"{name}: input_ids must be int64 or int32 [B, T], got {input_ids.dtype} {tuple(input_ids.shape)}")
+        cfg = self.config
+        B, T = input_ids.shape
+        dev = input_ids.device
+        Tp = max(SCORE_MIN_TOKENS, T) if is_decoder else T
+        enc = encoder_hidden_states if mode == "multimodal" else None
+        if enc is not None and not hasattr(self.encoder.layer[0], "crossattention"):
+            raise ValueError(f"{name}: encoder_hidden_states given to a model built without cross-attention layers")
+        if enc is not None and (enc.dim() != 3 or enc.shape[0] != B or enc.shape[2] != cfg.encoder_width or not enc.is_cuda):
+            raise ValueError(f"{name}: encoder_hidden_states must be [{B}, Te, {cfg.encoder_width}] on the device, got {tuple(enc.shape)}")
+        if attention_mask is not None and tuple(attention_mask.shape) != (B, T):
+            raise ValueError(f"{name}: attention_mask must be [{B}, {T}] of 0 / 1, got {tuple(attention_mask.shape)}")
+        if enc is not None and encoder_attention_mask is not None and tuple(encoder_attention_mask.shape) != (B, enc.shape[1]):
+            raise ValueError(f"{name}: encoder_attention_mask must be [{B}, {enc.shape[1]}] of 0 / 1, got "
+                             f"{tuple(encoder_attention_mask.shape)}")
+        # ---- the attention kernels' own limits
+        if Tp > self.LONG_KEYS:
+            raise K.VidilHipError(f"{name}: {B} x {T} tokens: self-attention over more than {self.LONG_KEYS} keys"
+                                  f"{' under a causal mask' if is_decoder else ''} is not served by the attention kernels")
+        if Tp > cfg.max_position_embeddings:
+            raise ValueError(f"{name}: a block of {Tp} tokens exceeds max_position_embeddings={cfg.max_position_embeddings}")
+        if enc is not None and enc.shape[1] > MAX_VIDEO_TOKENS:
+            raise K.VidilHipError(f"{name}: {T} query rows over {enc.shape[1]} encoder states: more than {MAX_VIDEO_TOKENS} keys are not "
+                                  "served by the attention kernels")
+        ids = input_ids.to(torch.int32)
+        keep = None if attention_mask is None else attention_mask.to(dev) != 0
+        if Tp != T:
+            ids = torch.cat([ids, torch.full((B, Tp - T), cfg.pad_token_id, dtype=torch.int32, device=dev)], 1)
+            keep = torch.arange(Tp, device=dev)[None, :].expand(B, -1) < T if keep is None else \
+                torch.cat([keep, torch.zeros((B, Tp - T), dtype=torch.bool, device=dev)], 1)
+        cross, ckl = (None, None) if enc is None else self._cross_for_forward(enc, encoder_attention_mask, B, Tp)
+        h32, h16 = self.embed(ids.reshape(-1).contiguous(), Tp, 0)
+        hidden = [h32.clone()] if output_hidden_states else None
+        h32, h16 = self.masked_pass(h32, h16, B, Tp, keep, causal=bool(is_decoder), cross=cross, cross_kv_len=ckl, hidden_out=hidden)
+
+        def cut(x):
+            x = x.view(B, Tp, -1)
+            return x if Tp == T else x[:, :T].contiguous()
+        return h32, h16, Tp, cut(h32), None if hidden is None else tuple(cut(x) for x in hidden)
+
+    @torch.no_grad()
+    def forward(self, input_ids=None, attention_mask=None, position_ids=None, head_mask=None, inputs_embeds=None,
+                encoder_embeds=None, encoder_hidden_states=None, encoder_attention_mask=None, past_key_values=None,
+                use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, is_decoder=False,
+                mode='multimodal'):
+        """The reference's call (models/med.py:670-807) over the library's kernels.
+
+        Served: input_ids int64 / int32 [B, T] on the device; attention_mask [B, T] of 0 / 1 (default: ones);
+        encoder_hidden_states f32 or 16-bit [B, Te, width] with encoder_attention_mask [B, Te] (default: ones); mode 'text'
+        (no cross-attention) or 'multimodal'; is_decoder False (bidirectional) or True (causal and padding mask, :609-668);
+        output_hidden_states; return_dict (None: True).  Returns an object with ``last_hidden_state`` f32 [B, T, C],
+        ``hidden_states`` (a tuple of L + 1 f32 [B, T, C] when asked, else None) and ``pooler_output`` None (no model here
+        builds the pooler); with return_dict=False the tuple (last_hidden_state, None[, hidden_states]).
+        Refused by a NotImplementedError that names the argument, before any launch: position_ids, head_mask, inputs_embeds,
+        encoder_embeds, past_key_values, use_cache=True, output_attentions=True, a list as encoder_hidden_states, and the
+        parity precision mode.
+
+        Masks (``masked_pass``).  A mask whose ones form a prefix of every row is what the kernels' ``kv_len`` expresses: the
+        call issues the launches of ``encode`` on the same ids and lengths, with the same bits.  is_decoder: the kernels and, for
+        the rows inside a sequence, the bits of the teacher-forced pass of ``BertLMHeadModel.score``; the self-attention launch
+        is not identical — ``kv_len`` is passed besides the causal mask (``score`` passes none), so that padded rows agree with
+        the reference too.  With a prefix mask EVERY row agrees with the reference, padded positions included.  With any other
+        0 / 1 pattern (left padding, holes) only the positions whose mask is 1 are specified.  A row whose mask is all zero is
+        outside the contract.  encoder_attention_mask: the same, on the encoder states of each batch element.
+        Limits (VidilHipError naming the shape, nothing launched): more than LONG_KEYS tokens; more than 16,384 encoder states.
+        Cost: the cross K | V of every layer are projected in every call (the library's own entry points project them once per
+        image).  No backward pass."""
+        refused = (("position_ids", position_ids), ("head_mask", head_mask), ("inputs_embeds", inputs_embeds),
+                   ("encoder_embeds", encoder_embeds), ("past_key_values", past_key_values), ("use_cache", use_cache),
+                   ("output_attentions", output_attentions))
+        _, _, _, last, hidden = self._forward_states("BertModel.forward", input_ids, attention_mask, encoder_hidden_states,
+                                                     encoder_attention_mask, bool(output_hidden_states), is_decoder, mode, refused)
+        if return_dict is not None and not return_dict:
+            return (last, None) + (() if hidden is None else (hidden,))
+        return ModelOutput(last_hidden_state=last, pooler_output=None, past_key_values=None, hidden_states=hidden,
+                           attentions=None, cross_attentions=None)
 
 
 class _LMTransform(nn.Module):
@@ -1099,23 +1296,10 @@ class BertLMHeadModel(PackedCache, nn.Module):
         return out[:n]
 
     def _causal_block_pass(self, ids_i32, rows, T, cross, **cross_kw):
-        """The ONE stack pass of ``score`` and ``start_logits``: ids i32 [rows*T] (device) -> (h32, h16) [rows*T, C] after a
-        causal pass in which every block of T tokens attends to itself through one scratch K / V^T pair shared by all layers
-        (as DecoderSession.prefill does for a prompt) and to ``cross`` (cross_kw: cross_index / cross_groups / cross_max_group /
-        cross_kv_len).  The stack is the one a DecoderSession runs (LN-folded or parity) — never a function of the batch."""
-        bert, cfg = self.bert, self.config
-        H, L = cfg.num_attention_heads, cfg.num_hidden_layers
-        dev = ids_i32.device
-        h32, h16 = bert.embed(ids_i32, T, 0)
-        cdt = h16.dtype
-        fused = (os.environ.get("VIDIL_DECODE_FUSE_LN", "1") != "0" and not bert.parity and bert._text_fold_ok(cdt)
-                 and cfg.add_cross_attention)
-        NPs = (T + 15) // 16 * 16
-        sk = torch.empty((1, rows, H, T, 64), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
-        sv = torch.empty((1, rows, H, 64, NPs), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
-        bert.run_layers(h32, h16, rows=rows, T=T, self_k=sk, self_vt=sv, t_off=0, Tk_cap=T, NPs=NPs, causal=True, kv_len=None,
-                        cross=cross, fused=fused, **cross_kw)
-        return h32, h16
+        """The ONE stack pass of ``score`` and ``start_logits``: ids i32 [rows*T] (device) -> (h32, h16) [rows*T, C] after the
+        embedding and ``BertModel.causal_pass``."""
+        h32, h16 = self.bert.embed(ids_i32, T, 0)
+        return self.bert.causal_pass(h32, h16, rows, T, cross, **cross_kw)
 
     @torch.no_grad()
     def start_logits(self, enc16, B, start_id, *, cross_kv_len=None):
@@ -1290,7 +1474,70 @@ class BertLMHeadModel(PackedCache, nn.Module):
         return CaptionScores(loss_sum=table.sum(1).float(), count=count, lp_label=lp, lp_mean=lpm, argmax=amax,
                              token_loss=token_loss, caption=caption_d, position=position_d)
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("BertLMHeadModel.forward (the HF signature) is not built: captions are generated by "
-                                  "vidil_amd.blip.BLIP_Decoder.generate and GIVEN captions are scored teacher-forced by "
-                                  "BertLMHeadModel.score / BLIP_Decoder.caption_nll (BLIP_Decoder.forward returns the loss)")
+    @torch.no_grad()
+    def forward(self, input_ids=None, attention_mask=None, position_ids=None, head_mask=None, inputs_embeds=None,
+                encoder_hidden_states=None, encoder_attention_mask=None, labels=None, past_key_values=None, use_cache=None,
+                output_attentions=None, output_hidden_states=None, return_dict=None, return_logits=False, is_decoder=True,
+                reduction='mean', mode='multimodal'):
+        """The reference's call (models/med.py:830-930) over the library's kernels: ``BertModel.forward`` (same served and
+        refused arguments, same mask contract) and the LM head on every position.
+
+        ``logits`` f32 [B, T, V]: the LM-head GEMMs over all rows (``lm_logits_rows``, in row blocks of LOGITS_BLOCK_BYTES of
+        scratch).  return_logits=True returns [B, T-1, V] and nothing else (:905-906).  With ``labels`` int [B, T] (-100:
+        ignored): ``loss``, the label-smoothed (0.1) cross-entropy of the logits at t against labels[t + 1], from the one-read
+        reduction of kernels.token_logprobs — reduction='mean': 0-dim, over the scored tokens; 'none': [B], the sum per sequence
+        (:909-917).  On right-padded captions these sums are the bits of ``score`` (loss_sum) on the same inputs (same kernels;
+        the self-attention launch also carries ``kv_len``, see ``BertModel.forward``).  The logits
+        of a position whose mask is 0 are outside the mask contract, so a label at t + 1 behind such a position (the first real
+        token of a left-padded sequence) belongs at -100, as a prompt's tokens are (models/blip.py:114).
+        Returns an object with ``loss``, ``logits``, ``hidden_states``; with return_dict=False the tuple ([loss,] logits[,
+        hidden_states]).  No backward pass: the results carry no graph."""
+        if reduction not in ("mean", "none"):
+            raise ValueError(f"BertLMHeadModel.forward: reduction={reduction!r} (mean | none)")
+        refused = (("position_ids", position_ids), ("head_mask", head_mask), ("inputs_embeds", inputs_embeds),
+                   ("past_key_values", past_key_values), ("use_cache", use_cache), ("output_attentions", output_attentions))
+        h32, h16, Tp, _, hidden = self.bert._forward_states("BertLMHeadModel.forward", input_ids, attention_mask,
+                                                            encoder_hidden_states, encoder_attention_mask,
+                                                            bool(output_hidden_states), is_decoder, mode, refused)
+        cfg = self.config
+        B, T = input_ids.shape
+        V = cfg.vocab_size
+        dev = h32.device
+        if labels is not None and tuple(labels.shape) != (B, T):
+            raise ValueError(f"BertLMHeadModel.forward: labels must be [{B}, {T}], got {tuple(labels.shape)}")
+        rows = (torch.arange(B, device=dev)[:, None] * Tp + torch.arange(T, device=dev)[None, :]).reshape(-1)
+        n = B * T
+        block = max(1, LOGITS_BLOCK_BYTES // (4 * V))
+        if block >= HEAD_GEMM_ROWS:
+            block = block // HEAD_GEMM_ROWS * HEAD_GEMM_ROWS
+        n_pad = (n + HEAD_GEMM_ROWS - 1) // HEAD_GEMM_ROWS * HEAD_GEMM_ROWS
+        if n_pad <= block:                  # (one block: the head writes the result's own storage)
+            store = torch.empty((n_pad, V), dtype=torch.float32, device=dev)
+            logits = self.lm_logits_rows(h16, rows, out=store, h32=h32)
+        else:
+            logits = torch.empty((n, V), dtype=torch.float32, device=dev)
+            # (the scratch of a block: its rows rounded up to whole HEAD_GEMM_ROWS-row launches, as score sizes its buffer)
+            need = (min(block, n) + HEAD_GEMM_ROWS - 1) // HEAD_GEMM_ROWS * HEAD_GEMM_ROWS
+            buf = torch.empty((need, V), dtype=torch.float32, device=dev)
+            for r0 in range(0, n, block):
+                logits[r0:r0 + block].copy_(self.lm_logits_rows(h16, rows[r0:r0 + block], out=buf, h32=h32))
+        if return_logits:
+            return logits.view(B, T, V)[:, :-1].contiguous()
+        loss = None
+        if labels is not None:
+            shifted = torch.full((B, T), -100, dtype=torch.int32, device=dev)
+            shifted[:, :-1] = labels.to(dev)[:, 1:].to(torch.int32)
+            shifted = torch.where(shifted < 0, torch.full_like(shifted, -100), shifted).view(-1).contiguous()
+            lp, lpm, _ = K.token_logprobs(logits, shifted)
+            token_loss = -((1.0 - 0.1) * lp + 0.1 * lpm)                # (ignored rows score exactly 0 in both)
+            if reduction == "none":
+                table = torch.zeros((B, T), dtype=torch.float64, device=dev)
+                table[:, 1:] = token_loss.view(B, T)[:, :-1].double()   # (at the TARGET token's position, as score does)
+                loss = table.sum(1).float()
+            else:
+                loss = (token_loss.double().sum() / ((shifted >= 0) & (shifted < V)).sum().clamp_min(1)).float()
+        logits = logits.view(B, T, V)
+        if return_dict is not None and not return_dict:
+            return (() if loss is None else (loss,)) + (logits,) + (() if hidden is None else (hidden,))
+        return ModelOutput(loss=loss, logits=logits, past_key_values=None, hidden_states=hidden, attentions=None,
+                           cross_attentions=None)
