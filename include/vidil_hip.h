@@ -304,6 +304,20 @@ int vidil_attention(const void* q, const void* k, const void* vt, void* out,
 /*   arith == 2, a value no caller built against the struct that ended at kv16  */
 /*   passes (it was VIDIL_EINVAL), so the library never reads past such a       */
 /*   caller's struct.                                                           */
+/*  pinned by tests/test_attention_f32_forms_gpu.py (every kernel, unit form    */
+/*  and output form, against fp64):                                             */
+/*   - a row with no admissible key (kv_len[b] == 0, or causal with             */
+/*     t + causal_off + 1 <= 0) is written as zeros - hi and lo - in every      */
+/*     dense form; query batches that no group of group_start names are not     */
+/*     written at all; columns behind H*64 of a row or plane are not written.   */
+/*   - causal_off may be negative (the first -causal_off rows then have no key).*/
+/*   - outputs that do not allow wide stores (ldo % 4 != 0 for f32 rows,        */
+/*     ldo % 12 != 0 for 16-bit planes, or out not 16-byte aligned): arith 0    */
+/*     runs its VALU kernel, which stores element by element; the MFMA kernel   */
+/*     of arith 1 and 2 refuses them (VIDIL_EINVAL, never a demotion to f32     */
+/*     arithmetic).  The one-row-per-unit kernel of arith 1 (Nq == 1 with       */
+/*     kv_group == 1 or kv_index) and the arena form store element by element   */
+/*     and take any ldo the out_mode admits.                                    */
 /* replaces (in that mode): models/vit.py:75-83; models/med.py:178-220; HF     */
 /* CLIPAttention.                                                              */
 /* ------------------------------------------------------------------------ */

@@ -2492,7 +2492,9 @@ extern "C" int vidil_attention_f32(const vidil_attn_f32_args* a, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const bool bf = a->dtype16 == VIDIL_DT_BF16;
   if (a->anc != nullptr) {
-    VIDIL_REQUIRE(a->Nq == 1 && a->arena_rows > 0 && a->anc_ld >= a->Nk, "attention_f32: the arena form serves one query row per batch");
+    VIDIL_REQUIRE(a->Nq == 1 && a->arena_rows > 0 && a->anc_ld >= a->Nk,
+                  "attention_f32: the arena form serves one query row per batch (Nq=%d) and needs arena_rows=%d > 0, anc_ld=%d >= Nk=%d", a->Nq,
+                  a->arena_rows, a->anc_ld, a->Nk);
     const int units = a->Bq * a->H;
     if (a->Nk <= 32 && a->ldq % 4 == 0) {     // (the decode steps of a caption search: max_length <= 32)
       if (bf) hipLaunchKernelGGL((attn_f32_arena_gather_kernel<bf16, 4>), dim3((units + 3) / 4), dim3(256), 0, s, p);
