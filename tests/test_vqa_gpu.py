@@ -422,6 +422,7 @@ def test_rank_of_a_question_does_not_depend_on_its_batch_bit_for_bit(small_med_j
 
 def test_refusals(small_med_json):
     from vidil_amd import kernels as K
+    from vidil_amd.med import CrossRoute, parity_layers
     from vidil_amd.packing import set_compute_dtype, set_parity_mode
 
     g = vc.golden()
@@ -442,10 +443,8 @@ def test_refusals(small_med_json):
         # the stack itself refuses a masked cross-attention in the parity mode
         dec = m.text_decoder
         with pytest.raises(K.VidilHipError, match="cross_kv_len"):
-            dec.bert._run_layers_parity(dec.bert.packed(), None, None, rows=1, T=1, self_k=None, self_vt=None, t_off=0, Tk_cap=1, NPs=0,
-                                        causal=True, kv_len=None, cross=None, cross_index=None, cross_group=1, cross_groups=None,
-                                        cross_max_group=0, ws=None, arena=None, arena_slot_stride=1,
-                                        cross_kv_len=torch.ones(1, dtype=torch.int32, device=DEV))
+            route = CrossRoute(dec.bert, None, 1, kv_len=torch.ones(1, dtype=torch.int32, device=DEV))
+            parity_layers(dec.bert, dec.bert.packed(), None, None, rows=1, T=1, causal=True, kv_len=None, route=route)
     finally:
         set_parity_mode(False, m.text_decoder)
     assert int(m(img, vc.questions(g), vc.answers(g), train=False, inference="rank", k_test=8)[0]) == int(g["max_ids"][0])

@@ -112,8 +112,7 @@ class DecoderSession:
         # round 6: the decoder's post-LN stack without LayerNorm launches (BertModel._run_layers_fused: raw sums + row partials
         # between the GEMMs, the LayerNorms folded into the consuming / residual GEMMs) — a property of the SESSION, never of its
         # size: a caption must not depend on how many images share its search ($VIDIL_DECODE_FUSE_LN=0: the unfused launches)
-        self.fused_ln = (os.environ.get("VIDIL_DECODE_FUSE_LN", "1") != "0" and not self.bert.parity
-                         and self.bert._text_fold_ok(enc16.dtype) and cfg.add_cross_attention)
+        self.fused_ln = self.bert.decoder_fused_ln(enc16.dtype)
 
     @classmethod
     def like(cls, parent, B):
@@ -127,7 +126,7 @@ class DecoderSession:
         pc = parent.cross
         self.cross = CrossKV(torch.empty((pc.k.shape[0], B) + tuple(pc.k.shape[2:]), dtype=pc.k.dtype, device=pc.k.device),
                              torch.empty((pc.vt.shape[0], B) + tuple(pc.vt.shape[2:]), dtype=pc.vt.dtype, device=pc.vt.device),
-                             B, pc.Te, pc.NP, tiled=pc.tiled, Tk_cap=pc.Tk_cap, f32=getattr(pc, "f32", False))
+                             B, pc.Te, pc.NP, tiled=pc.tiled, Tk_cap=pc.Tk_cap, f32=pc.f32)
         pa = parent.arena
         self.arena = BeamArena(pa.L, pa.Tcap, self.R, pa.k.shape[-1], pa.k.device, dtype=pa.k.dtype)
         self.ws_prefill, self.ws_step = {}, {}
@@ -165,13 +164,9 @@ class DecoderSession:
         image nb times), so their prompt pass is computed once and its K/V are stored once (arena slot b*nb, which
         the ancestry rows of all nb beams point at)."""
         rows = self.B if shared else self.R
-        dev = ids_i32.device
         h32, h16 = self.bert.embed(ids_i32, P, 0)
-        cdt = h16.dtype
-        NPp = (P + 15) // 16 * 16
         # the prompt block attends to itself through one scratch K / V^T pair shared by all layers
-        sk = torch.empty((1, rows, self.H, P, 64), dtype=cdt, device=dev).expand(self.L, -1, -1, -1, -1)
-        sv = torch.empty((1, rows, self.H, 64, NPp), dtype=cdt, device=dev).expand(self.L, -1, -1, -1, -1)
+        sk, sv, NPp = self.bert.scratch_kv(rows, P, h16.dtype, ids_i32.device)
         self.arena.init_prompt(P, self.nb if shared else 1)
         self.bert.run_layers(h32, h16, rows=rows, T=P, self_k=sk, self_vt=sv, t_off=0, Tk_cap=P, NPs=NPp, causal=True,
                              kv_len=None, cross=self.cross, cross_group=1 if shared else self.nb, ws=self.ws_prefill,

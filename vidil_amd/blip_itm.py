@@ -150,7 +150,7 @@ class BLIP_ITM(PackedCache, nn.Module):
         # image-major groups with more than 32 query rows go through the staged attention kernel, which takes V
         # row-major (plain 16-B stores from the K|V GEMM instead of the V^T scatter)
         rows_per_image = (max_group if group_start is not None else 1) * t_eff
-        long_keys = Te > te.LONG_KEYS        # (BertModel._cross_bound then rounds every launch's bound up past 32 rows)
+        long_keys = Te > te.LONG_KEYS        # (CrossRoute.bound then rounds every launch's bound up past 32 rows)
         if long_keys and group_start is None:
             raise K.VidilHipError(f"itm_pairs: {Te} > {te.LONG_KEYS} tokens per image need image-major pairs: use group_start "
                                   "(the image_index form has one pair's rows per unit)")
@@ -171,7 +171,7 @@ class BLIP_ITM(PackedCache, nn.Module):
         p = self.packed()
         if p["parity"]:
             # parity precision mode (packing.set_parity_mode): every pair through the stack with error-compensated GEMM operands
-            # (_run_layers_parity), no shared text front.  With the f32-row attention kinds the last layer runs on the [CLS] rows
+            # (med.parity_layers), no shared text front.  With the f32-row attention kinds the last layer runs on the [CLS] rows
             # alone (BertModel.encode_cls_parity); kind "16" takes every token through every layer (BertModel.encode)
             if pair_text is not None:
                 ids, lens = ids.index_select(0, pair_text).contiguous(), lens.index_select(0, pair_text).contiguous()

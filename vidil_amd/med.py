@@ -198,6 +198,79 @@ class CrossKV:
         self.last_vt, self.last_NP = last_vt, last_NP
 
 
+class CrossRoute:
+    """The cross-attention side of one stack pass: the ``CrossKV`` (None: a pass without cross-attention) and which encoder unit
+    each of the pass's ``rows`` query batches attends to — unit ``index[r]`` (i32 [rows], device); or, image-major order, unit j
+    serves batches groups[j] .. groups[j+1]-1 (i32 [B+1], at most ``max_group`` each); or unit r // group.  ``kv_len`` (i32
+    [rows], device; None: every one of cross.Te keys): batch r attends to the first kv_len[r] keys of its unit only.
+    Building one allocates nothing, launches nothing and waits for nothing (a decode step builds its route under graph capture);
+    ``model`` is read for LONG_KEYS and MAX_IMAGES_PER_LAUNCH, as they stand when the pass starts."""
+
+    def __init__(self, model, cross, rows, *, index=None, group=1, groups=None, max_group=0, kv_len=None):
+        self.cross, self.rows = cross, rows
+        self.index, self.group, self.groups, self.max_group, self.kv_len = index, group, groups, max_group, kv_len
+        self.long_keys, self.images_per_launch = model.LONG_KEYS, model.MAX_IMAGES_PER_LAUNCH
+        if kv_len is not None and (kv_len.dtype != torch.int32 or kv_len.dim() != 1 or kv_len.numel() != rows or not kv_len.is_contiguous()):
+            raise K.VidilHipError(f"run_layers: cross_kv_len must be a contiguous i32 [{rows}] tensor (one length per query batch), got "
+                                  f"{kv_len.dtype} {tuple(kv_len.shape)}")
+
+    @property
+    def tiled(self):
+        """The ``kv_tiled`` selector of a launch: 2 (key-split form allowed) for fragment tiles over more than LONG_KEYS encoder
+        states; otherwise what it always was, so launches over up to LONG_KEYS states are unchanged."""
+        return 2 if self.cross.tiled and self.cross.Te > self.long_keys else self.cross.tiled
+
+    def bound(self, Nq):
+        """The ``max_group`` bound of a launch with Nq query rows per batch.  Up to LONG_KEYS encoder states it is the caller's;
+        over more (a video's frames concatenated as one encoder sequence) plain K / V are served by the long-key form, for which
+        every launch must present more than 32 query rows per unit, so the bound of the ``groups`` form is rounded up to
+        ceil(33 / Nq) — it is an upper bound, row tiles past a unit's last row return at once — and the other forms are refused
+        where they cannot reach 33 rows.  Fragment tiles (a decoder session's) are served by the key-split form, at most 32 rows
+        per unit: the bound stays the caller's, and more rows are refused."""
+        Te = self.cross.Te
+        if Te <= self.long_keys:
+            return self.max_group
+        if self.cross.tiled:
+            rows = Nq * (self.max_group if self.groups is not None else 1 if self.index is not None else self.group)
+            if rows > 32:
+                raise K.VidilHipError(f"cross-attention over {Te} > {self.long_keys} encoder states in fragment tiles serves at most "
+                                      f"32 query rows per unit (got {rows}): build the session with tiled_cross=False, whose launches "
+                                      "go to the long-key form")
+            return self.max_group
+        if self.groups is not None:
+            return max(self.max_group, -(-33 // Nq))
+        rows = Nq * (1 if self.index is not None else self.group)
+        if rows <= 32:
+            raise K.VidilHipError(f"cross-attention over {Te} > {self.long_keys} encoder states needs more than 32 query rows per "
+                                  f"unit (got {rows}): order the pairs image-major and use group_start")
+        return self.max_group
+
+    def blocks(self):
+        """(b0, b1, r0, r1) of the launches of one layer: units [b0, b1) serve query batches [r0, r1).  One launch over every
+        batch, whatever maps batches to units; or — uniform grouping (a beam search) over more than MAX_IMAGES_PER_LAUNCH images
+        — blocks of that many images, each a launch over contiguous slices of Q, K, V and the output rows."""
+        B, n = self.cross.B, self.images_per_launch
+        if self.index is not None or self.groups is not None or B <= n:
+            return [(0, B, 0, self.rows)]
+        return [(b0, min(B, b0 + n), b0 * self.group, min(B, b0 + n) * self.group) for b0 in range(0, B, n)]
+
+    def len_arg(self, r0, r1):
+        """The ``kv_len`` keyword of a launch over query batches r0 .. r1-1: nothing for a route without kv_len (the launch then
+        is exactly what it was before the argument existed), else its slice of the table."""
+        return {} if self.kv_len is None else dict(kv_len=self.kv_len[r0:r1])
+
+    def attend(self, i, q, o, T):
+        """The plain 16-bit cross-attention launches of layer i: q [rows, H, T, 64] -> o [rows*T, C].  Every query batch that
+        shares an image (the beams of a caption search, the captions of a frame) is served by one fetch of that image's K/V:
+        see vidil_attention's grouping forms."""
+        c = self.cross
+        mg = self.bound(T)
+        for b0, b1, r0, r1 in self.blocks():
+            K.attention(q[r0:r1], c.k[i][b0:b1], c.vt[i][b0:b1], o[r0 * T:r1 * T], Bq=r1 - r0, H=q.shape[1], Nq=T, Nk=c.Te, Tq_cap=T,
+                        Tk_cap=c.Tk_cap, NP=c.NP, kv_group=self.group, kv_index=self.index, group_start=self.groups, max_group=mg,
+                        kv_tiled=self.tiled, **self.len_arg(r0, r1))
+
+
 class BeamArena:
     """Append-only self-attention K/V of a beam search (all layers): k, v f16 [L][Tcap][rows][H*64], written at
     [position][slot = producing beam row]; ``anc`` i32 [rows][Tcap] maps (beam row, position) -> slot and is the
@@ -224,6 +297,140 @@ class BeamArena:
         """Beam row r now continues old row beam_idx[r]; its next K/V (position cur_pos) go to slot r."""
         K.beam_ancestry(self._anc[self._cur], self._anc[self._cur ^ 1], beam_idx_i32, cur_pos)
         self._cur ^= 1
+
+
+def parity_layers(model, p, h32, h3, *, rows, T, causal, kv_len, route=None, self_k=None, self_vt=None, t_off=0, Tk_cap=None, NPs=0,
+                  ws=None, arena=None, arena_slot_stride=1, n_layers=None, rel_bias=None, rel_off=None):
+    """BertModel.run_layers in the parity precision mode, on the packed layers ``p["layers"]``: ``h3`` [rows*T, 3C] carries the
+    hidden states as [hi | lo | hi] operand rows, every GEMM runs against [W_hi | W_hi | W_lo] with K tripled, LayerNorm /
+    attention write split rows directly and the GELU output goes through f32 + vidil_split3_f32.  Same launch sequence otherwise.
+    Of ``model`` it needs config.num_attention_heads / hidden_size / intermediate_size / layer_norm_eps and the parity-attention
+    setting packing keeps for it (parity_attention_f32 / parity_attention_arith): a BertModel, or vidil_amd/sentence.py's
+    encoder, which runs this sequence as the layers of MPNet.
+    route: the pass's CrossRoute (None: no cross-attention).  self_k / self_vt / Tk_cap / NPs: attention kind "16" only.
+    n_layers: only the first n layers (encode_cls_parity runs the last itself); ws["planes_h"] then tells it how many
+    planes of ``h3`` the last of them wrote.
+    rel_bias / rel_off: a relative-position bias table for the block self-attention of every layer (kernels.attention_f32's
+    arguments; the f32-row attention kinds only)."""
+    cross = None if route is None else route.cross
+    if rel_bias is not None and (not parity_attention_f32(model) or arena is not None or cross is not None):
+        raise K.VidilHipError("_run_layers_parity: rel_bias serves the f32-row self-attention of a stack without cross-attention or arena")
+    if route is not None and route.kv_len is not None:
+        raise K.VidilHipError("_run_layers_parity: cross_kv_len (masked cross-attention) is not built for the parity precision mode")
+    cfg = model.config
+    H, C = cfg.num_attention_heads, cfg.hidden_size
+    eps = cfg.layer_norm_eps
+    M = rows * T
+    dev, cdt = h32.device, h3.dtype
+    if ws is None:
+        ws = {}
+    q = ws.get("q")
+    if q is None or q.shape[0] < rows or q.shape[2] != T:
+        q = torch.empty((rows, H, T, 64), dtype=cdt, device=dev)
+        ws["q"] = q
+    o3 = torch.empty((M, 3 * C), dtype=cdt, device=dev)
+    tmp = torch.empty((M, C), dtype=torch.float32, device=dev)
+    inter3 = torch.empty((M, 3 * cfg.intermediate_size), dtype=cdt, device=dev)
+    # Which producers may leave the third plane of their [hi | lo | hi] rows unwritten (ADVICE r5): only those whose EVERY
+    # consumer takes the K-loop form of the compensated product, asked per CALL (K.split_k_serves).  inter3 feeds fc2 (f32
+    # epilogue); with the f32-row attention kinds h3 / o3 feed Q|K|V, the cross query, both output projections and fc1, all
+    # with the f32 epilogue; kind "16" feeds h3 to arena / short-sequence scatter epilogues, which run the plain K = 3 Kl
+    # product over all three planes.  The consumers state a_planes, so a launch that would read an unwritten plane fails
+    # (EINVAL) instead of computing on it.
+    f32_attn, arith = parity_attention_f32(model), parity_attention_arith(model)
+    qkv32 = torch.empty((M, 3 * C), dtype=torch.float32, device=dev) if f32_attn else None
+    q32 = torch.empty((M, C), dtype=torch.float32, device=dev) if f32_attn and cross is not None else None
+    d0 = p["layers"][0]
+    planes = planes_h = 3
+    if K.split_k_serves(inter3, d0["o_w3"], d0["o_b"], out=tmp, resid=h32):
+        planes = 2
+    if f32_attn and planes == 2 and all((
+            K.split_k_serves(h3, d0["qkv_w3"], d0["qkv_b"], out=qkv32),
+            K.split_k_serves(o3, d0["ao_w3"], d0["ao_b"], out=tmp, resid=h32),
+            K.split_k_serves(h3, d0["i_w3"], d0["i_b"], split3_out=inter3, act=K.ACT_GELU_ERF),
+            cross is None or K.split_k_serves(h3, d0["cq_w3"], d0["cq_b"], out=q32))):
+        planes_h = 2
+    K.poison_third_plane(planes, inter3)
+    K.poison_third_plane(planes_h, o3, h3)
+    ws["planes_h"] = planes_h
+    Nk = t_off + T
+    # The three cross launches below are this sequence's own, NOT CrossRoute.attend: they pass the caller's max_group and
+    # cross.tiled unmodified (no CrossRoute.bound, no kv_tiled = 2) and only the kv16 branch walks the route's blocks, so past
+    # LONG_KEYS keys, or past MAX_IMAGES_PER_LAUNCH images outside kv16, the parity mode lacks what the plain stacks do.
+    if f32_attn:
+        # Q | K | V (and the cross query) stay f32 and row-major, the KV arena and the cross K | V are f32:
+        # vidil_attention_f32 reads all of them in place.  (t_off > 0 happens in the arena form only.)
+        # (split-operand kind: the cross K | V of a decoder session are 16-bit fragment tiles instead)
+        kv16 = cross is not None and arith == 1 and cross.tiled and not cross.f32
+        if (arena is not None and arena.k.dtype != torch.float32) or (cross is not None and not cross.f32 and not kv16):
+            raise K.VidilHipError("run_layers (parity mode, f32 attention): the KV arena / cross K|V of this session were built for "
+                                  "the 16-bit attention kernels — build the DecoderSession / CrossKV under the same $VIDIL_PARITY_ATTN")
+        if t_off != 0 and not (arena is not None and T == 1):
+            raise K.VidilHipError("run_layers (parity mode, f32 attention): cached self-attention keys are served by the arena form only")
+        if kv16 and T * max(1, route.group) > 32 and route.groups is None and route.index is None:
+            # (ADVICE r5: the kv16 form serves at most 32 query rows per image — a DecoderSession's decode steps and shared
+            #  prompt pass; a longer prompt x group must be built with the f32-row cross K|V instead)
+            raise K.VidilHipError(f"run_layers (parity mode, split attention): {T} tokens x {route.group} sequences per image exceed the 32 "
+                                  "query rows per image the 16-bit cross K/V tiles serve — build the session with tiled_cross=False")
+    for i, d in enumerate(p["layers"][:n_layers]):
+        if f32_attn:
+            K.gemm(h3, d["qkv_w3"], d["qkv_b"], out=qkv32, split_k=True, a_planes=planes_h)
+            if arena is not None and T == 1:
+                arena.k[i][t_off].copy_(qkv32[:, C:2 * C])          # position t_off, slot = producing beam row
+                arena.v[i][t_off].copy_(qkv32[:, 2 * C:])
+                K.attention_f32(qkv32[:, :C], arena.k[i], arena.v[i], o3, Bq=rows, H=H, Nq=1, Nk=Nk, anc=arena.anc,
+                                arena_rows=arena.rows, planes=planes_h)
+            else:
+                K.attention_f32(qkv32[:, :C], qkv32[:, C:2 * C], qkv32[:, 2 * C:], o3, Bq=rows, H=H, Nq=T, Nk=T, causal=causal,
+                                kv_len=kv_len, arith=arith, planes=planes_h, rel_bias=rel_bias, rel_off=rel_off)
+                if arena is not None:   # the prompt's K / V in the arena: position t, slot r * arena_slot_stride
+                    blk = qkv32.view(rows, T, 3 * C)
+                    arena.k[i][:T, 0:rows * arena_slot_stride:arena_slot_stride] = blk[:, :, C:2 * C].permute(1, 0, 2)
+                    arena.v[i][:T, 0:rows * arena_slot_stride:arena_slot_stride] = blk[:, :, 2 * C:].permute(1, 0, 2)
+        elif arena is not None and T == 1:
+            K.gemm(h3, d["qkv_w3"], d["qkv_b"], split_k=True,
+                   arena=dict(q=q, k=arena.k[i], v=arena.v[i], T=1, H=H, part0=0, t_off=t_off, Tcap=arena.Tcap,
+                              arena_rows=arena.rows, slot_stride=1, q_scale=0.125))
+            K.beam_attention(q, arena.k[i], arena.v[i], arena.anc, o3, rows=rows, H=H, n_keys=Nk, split3=True)
+        else:
+            K.gemm(h3, d["qkv_w3"], d["qkv_b"], split_k=True,
+                   heads=dict(q=q, k=self_k[i], vt=self_vt[i], T=T, H=H, part0=0, t_off=t_off, Tq_cap=T,
+                              Tk_cap=Tk_cap, NP=NPs, q_scale=0.125))
+            K.attention(q, self_k[i], self_vt[i], o3, Bq=rows, H=H, Nq=T, Nk=Nk, Tq_cap=T, Tk_cap=Tk_cap, NP=NPs,
+                        causal=causal, causal_off=t_off, kv_len=kv_len, split3=True)
+            if arena is not None:
+                K.gemm(h3, d["qkv_w3"][C:], d["qkv_b"][C:], split_k=True,
+                       arena=dict(k=arena.k[i], v=arena.v[i], T=T, H=H, part0=1, t_off=0, Tcap=arena.Tcap,
+                                  arena_rows=arena.rows, slot_stride=arena_slot_stride))
+        K.gemm(o3, d["ao_w3"], d["ao_b"], out=tmp, resid=h32, split_k=True, a_planes=planes_h)
+        K.layernorm(tmp, d["ao_g"], d["ao_bt"], eps, out16=h3, out32=h32, split3=True, planes=planes_h)
+        if cross is not None and f32_attn:
+            K.gemm(h3, d["cq_w3"], d["cq_b"], out=q32, split_k=True, a_planes=planes_h)
+            if kv16:
+                for b0, b1, r0, r1 in route.blocks():
+                    K.attention_f32(q32[r0 * T:r1 * T], cross.k[i][b0:b1], cross.vt[i][b0:b1], o3[r0 * T:r1 * T], Bq=r1 - r0, H=H, Nq=T, Nk=cross.Te,
+                                    kv_rows=cross.Tk_cap, kv_group=route.group, kv_index=route.index, group_start=route.groups,
+                                    max_group=route.max_group, arith=1, kv16=True, planes=planes_h)
+            else:
+                kv = cross.k[i]                                     # f32 [B, Te, 2C]: keys | values
+                K.attention_f32(q32, kv[..., :C], kv[..., C:], o3, Bq=rows, H=H, Nq=T, Nk=cross.Te, kv_rows=cross.Te,
+                                kv_group=route.group, kv_index=route.index, group_start=route.groups, max_group=route.max_group,
+                                arith=arith, planes=planes_h)
+            K.gemm(o3, d["co_w3"], d["co_b"], out=tmp, resid=h32, split_k=True, a_planes=planes_h)
+            K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=h3, out32=h32, split3=True, planes=planes_h)
+        elif cross is not None:
+            K.gemm(h3, d["cq_w3"], d["cq_b"], heads=dict(q=q, T=T, H=H, part0=0, Tq_cap=T, q_scale=0.125), split_k=True)
+            # (project_cross_kv(last_layer_vt=True) keeps the LAST layer's values in a V^T buffer of their own)
+            last = i == len(p["layers"]) - 1 and cross.last_vt is not None
+            K.attention(q, cross.k[i], cross.last_vt if last else cross.vt[i], o3, Bq=rows, H=H, Nq=T, Nk=cross.Te, Tq_cap=T,
+                        Tk_cap=cross.Tk_cap, NP=cross.last_NP if last else cross.NP, kv_group=route.group, kv_index=route.index,
+                        group_start=route.groups, max_group=route.max_group, kv_tiled=cross.tiled, split3=True)
+            K.gemm(o3, d["co_w3"], d["co_b"], out=tmp, resid=h32, split_k=True)
+            K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=h3, out32=h32, split3=True, planes=planes_h)
+        K.gemm(h3, d["i_w3"], d["i_b"], split3_out=inter3, act=K.ACT_GELU_ERF, split_k=True, split3_planes=planes, a_planes=planes_h)
+        K.gemm(inter3, d["o_w3"], d["o_b"], out=tmp, resid=h32, split_k=True, a_planes=planes)
+        K.layernorm(tmp, d["o_g"], d["o_bt"], eps, out16=h3, out32=h32, split3=True, planes=planes_h)
+    return h32, h3
 
 
 class BertModel(PackedCache, nn.Module):
@@ -341,7 +548,7 @@ class BertModel(PackedCache, nn.Module):
             if parity_attention_f32(self) and not (tiled and parity_attention_arith(self) == 1):
                 L, C = len(p["layers"]), self.config.hidden_size
                 dev = enc16.device
-                if out is not None and getattr(out, "f32", False) and (out.B, out.Te) == (B, Te) and out.k.device == dev:
+                if out is not None and out.f32 and (out.B, out.Te) == (B, Te) and out.k.device == dev:
                     kv32, ph = out.k, out.vt
                 else:
                     kv32 = torch.empty((L, B, Te, 2 * C), dtype=torch.float32, device=dev)
@@ -401,7 +608,7 @@ class BertModel(PackedCache, nn.Module):
     def run_layers(self, h32, h16, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len,
                    cross: CrossKV, cross_index=None, cross_group=1, cross_groups=None, cross_max_group=0, ws=None,
                    arena: "BeamArena" = None, arena_slot_stride=1, n_layers=None, self_done_first=False,
-                   stop_after_self=False, fused=None, cross_kv_len=None, arena_prompt=False, hidden_out=None):
+                   stop_after_self=False, fused=None, cross_kv_len=None, arena_prompt=False, hidden_out=None, route=None):
         """Run every layer on the f32/f16 hidden pair (both [rows*T, C], updated in place).
 
         self_k / self_vt: [L][rows,H,Tk_cap,64] / [L][rows,H,64,NPs] — this call's keys are appended at
@@ -417,6 +624,9 @@ class BertModel(PackedCache, nn.Module):
 
         cross_kv_len (i32 [rows], device; default None: every one of cross.Te keys): query batch r attends to the first
         cross_kv_len[r] keys of its encoder unit only (a decoder over padded question states: models/blip_vqa.py:69-76,125-129).
+
+        route: the CrossRoute of ``cross``, from a caller that built it already — instead of the cross_* keywords, of which this
+        call otherwise builds it, once.
 
         hidden_out (a list; BertModel.forward(output_hidden_states=True)): receives a f32 [rows*T, C] copy of the normalised
         hidden states after every layer run.  Not built for the parity precision mode.
@@ -439,10 +649,15 @@ class BertModel(PackedCache, nn.Module):
                 raise K.VidilHipError("run_layers: cross_kv_len (masked cross-attention) is not built for the parity precision mode")
             if arena_prompt:
                 raise K.VidilHipError("run_layers: a one-token prompt block (arena_prompt) is not built for the parity precision mode")
-            return self._run_layers_parity(p, h32, h16, rows=rows, T=T, self_k=self_k, self_vt=self_vt, t_off=t_off,
-                                           Tk_cap=Tk_cap, NPs=NPs, causal=causal, kv_len=kv_len, cross=cross,
-                                           cross_index=cross_index, cross_group=cross_group, cross_groups=cross_groups,
-                                           cross_max_group=cross_max_group, ws=ws, arena=arena, arena_slot_stride=arena_slot_stride)
+        if arena is not None and T > 1 and t_off != 0:
+            raise K.VidilHipError("run_layers: a multi-token block can only be appended to a beam arena at position 0")
+        if route is None:
+            route = CrossRoute(self, cross, rows, index=cross_index, group=cross_group, groups=cross_groups, max_group=cross_max_group,
+                               kv_len=cross_kv_len)
+        if p["parity"]:
+            return parity_layers(self, p, h32, h16, rows=rows, T=T, causal=causal, kv_len=kv_len, route=route, self_k=self_k,
+                                 self_vt=self_vt, t_off=t_off, Tk_cap=Tk_cap, NPs=NPs, ws=ws, arena=arena,
+                                 arena_slot_stride=arena_slot_stride)
         if fused is None:
             # encoder batches with cross-attention (the ITM pairs) run without LayerNorm launches, WHATEVER their size: a
             # pair's logits must not depend on how many other pairs share its batch (ranks / tail batches of different
@@ -454,11 +669,9 @@ class BertModel(PackedCache, nn.Module):
                                   "hidden_size % 64 == 0, <= 1024")
         if fused:
             return self._run_layers_fused(h32, h16, rows=rows, T=T, self_k=self_k, self_vt=self_vt, t_off=t_off, Tk_cap=Tk_cap,
-                                          NPs=NPs, causal=causal, kv_len=kv_len, cross=cross, cross_index=cross_index,
-                                          cross_group=cross_group, cross_groups=cross_groups, cross_max_group=cross_max_group,
-                                          n_layers=n_layers, self_done_first=self_done_first, arena=arena,
-                                          arena_slot_stride=arena_slot_stride, cross_kv_len=cross_kv_len, arena_prompt=arena_prompt,
-                                          hidden_out=hidden_out)
+                                          NPs=NPs, causal=causal, kv_len=kv_len, route=route, n_layers=n_layers,
+                                          self_done_first=self_done_first, arena=arena, arena_slot_stride=arena_slot_stride,
+                                          arena_prompt=arena_prompt, hidden_out=hidden_out)
         if ws is None:
             ws = {}
         q = ws.get("q")
@@ -469,9 +682,6 @@ class BertModel(PackedCache, nn.Module):
         tmp = torch.empty((M, C), dtype=torch.float32, device=dev)
         inter = torch.empty((M, cfg.intermediate_size), dtype=cdt, device=dev)
         Nk = t_off + T
-        if arena is not None and T > 1 and t_off != 0:
-            raise K.VidilHipError("run_layers: a multi-token block can only be appended to a beam arena at position 0")
-        ckl = self._cross_len_arg(cross_kv_len, rows)
         # n_layers: only the first n (encode_cls runs the last itself).  self_done_first / stop_after_self split layer
         # 0 after its self-attention block (dense + residual + LayerNorm included): that block does not see the image,
         # so encode_cls runs it once per TEXT and the rest of the stack once per (image, text) pair.
@@ -499,15 +709,8 @@ class BertModel(PackedCache, nn.Module):
             if stop_after_self:
                 break
             if cross is not None:
-                # every query batch that shares an image (the beams of a caption search, the captions of a
-                # frame) is served by one fetch of that image's K/V: see vidil_attention's grouping forms
                 K.gemm(h16, d["cq_w"], d["cq_b"], heads=dict(q=q, T=T, H=H, part0=0, Tq_cap=T, q_scale=0.125))
-                mg = self._cross_bound(cross, T, cross_index, cross_group, cross_groups, cross_max_group)
-                for b0, b1 in self._cross_blocks(cross, cross_index, cross_groups):
-                    r0, r1 = (0, rows) if (b0, b1) == (0, cross.B) else (b0 * cross_group, b1 * cross_group)
-                    K.attention(q[r0:r1], cross.k[i][b0:b1], cross.vt[i][b0:b1], o[r0 * T:r1 * T], Bq=r1 - r0, H=H, Nq=T, Nk=cross.Te,
-                                Tq_cap=T, Tk_cap=cross.Tk_cap, NP=cross.NP, kv_group=cross_group, kv_index=cross_index,
-                                group_start=cross_groups, max_group=mg, kv_tiled=self._cross_tiled(cross), **ckl(r0, r1))
+                route.attend(i, q, o, T)
                 K.gemm(o, d["co_w"], d["co_b"], out=tmp, resid=h32)
                 K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=h16, out32=h32)
             K.gemm(h16, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
@@ -521,192 +724,28 @@ class BertModel(PackedCache, nn.Module):
     #: the key-split form at most 32 on fragment tiles (a decoder session's: kv_tiled = 2)
     LONG_KEYS = 768
 
-    def _cross_tiled(self, cross):
-        """The ``kv_tiled`` selector of a cross-attention launch: 2 (key-split form allowed) for fragment tiles over more than
-        LONG_KEYS encoder states; otherwise what it always was, so launches over up to LONG_KEYS states are unchanged."""
-        return 2 if cross.tiled and cross.Te > self.LONG_KEYS else cross.tiled
-
-    def _cross_bound(self, cross, Nq, cross_index, cross_group, cross_groups, cross_max_group):
-        """The ``max_group`` bound of a cross-attention launch.  Up to LONG_KEYS encoder states it is the caller's; over more (a
-        video's frames concatenated as one encoder sequence) plain K / V are served by the long-key form, for which every launch
-        must present more than 32 query rows per unit, so the bound of the ``group_start`` form is rounded up to ceil(33 / Nq) — it
-        is an upper bound, row tiles past a unit's last row return at once — and the other forms are refused where they cannot
-        reach 33 rows.  Fragment tiles (a decoder session's) are served by the key-split form, at most 32 rows per unit: the
-        bound stays the caller's, and more rows are refused."""
-        if cross.Te <= self.LONG_KEYS:
-            return cross_max_group
-        if cross.tiled:
-            rows = Nq * (cross_max_group if cross_groups is not None else 1 if cross_index is not None else cross_group)
-            if rows > 32:
-                raise K.VidilHipError(f"cross-attention over {cross.Te} > {self.LONG_KEYS} encoder states in fragment tiles serves at most "
-                                      f"32 query rows per unit (got {rows}): build the session with tiled_cross=False, whose launches "
-                                      "go to the long-key form")
-            return cross_max_group
-        if cross_groups is not None:
-            return max(cross_max_group, -(-33 // Nq))
-        rows = Nq * (1 if cross_index is not None else cross_group)
-        if rows <= 32:
-            raise K.VidilHipError(f"cross-attention over {cross.Te} > {self.LONG_KEYS} encoder states needs more than 32 query rows per "
-                                  f"unit (got {rows}): order the pairs image-major and use group_start")
-        return cross_max_group
-
-    @staticmethod
-    def _cross_len_arg(cross_kv_len, rows):
-        """(r0, r1) -> the ``kv_len`` keyword of a cross-attention launch over query batches r0 .. r1-1: nothing when the call has
-        no cross_kv_len (the launch then is exactly what it was before the argument existed), else its slice of the table."""
-        if cross_kv_len is None:
-            return lambda r0, r1: {}
-        if cross_kv_len.dtype != torch.int32 or cross_kv_len.dim() != 1 or cross_kv_len.numel() != rows or not cross_kv_len.is_contiguous():
-            raise K.VidilHipError(f"run_layers: cross_kv_len must be a contiguous i32 [{rows}] tensor (one length per query batch), got "
-                                  f"{cross_kv_len.dtype} {tuple(cross_kv_len.shape)}")
-        return lambda r0, r1: dict(kv_len=cross_kv_len[r0:r1])
-
-    def _cross_blocks(self, cross, cross_index, cross_groups):
-        """Image ranges [b0, b1) of the cross-attention launches of one layer: the whole batch, or — uniform grouping (a beam
-        search: image b serves query batches b * group .. b * group + group - 1) over more than MAX_IMAGES_PER_LAUNCH images —
-        blocks of that many images, each a launch over contiguous slices of Q, K, V and the output rows."""
-        B, n = cross.B, self.MAX_IMAGES_PER_LAUNCH
-        if cross_index is not None or cross_groups is not None or B <= n:
-            return [(0, B)]                           # (one launch over every query row, whatever maps rows to images)
-        return [(b0, min(B, b0 + n)) for b0 in range(0, B, n)]
-
-    def _run_layers_parity(self, p, h32, h3, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len, cross, cross_index,
-                           cross_group, cross_groups, cross_max_group, ws, arena, arena_slot_stride, n_layers=None, cross_kv_len=None,
-                           rel_bias=None, rel_off=None):
-        """run_layers in the parity precision mode: ``h3`` [rows*T, 3C] carries the hidden states as [hi | lo | hi]
-        operand rows, every GEMM runs against [W_hi | W_hi | W_lo] with K tripled, LayerNorm / attention write split rows
-        directly and the GELU output goes through f32 + vidil_split3_f32.  Same launch sequence otherwise.
-        n_layers: only the first n layers (encode_cls_parity runs the last itself); ws["planes_h"] then tells it how many
-        planes of ``h3`` the last of them wrote.
-        rel_bias / rel_off (vidil_amd/sentence.py, which runs this sequence as the layers of MPNet): a relative-position bias table
-        for the block self-attention of every layer (kernels.attention_f32's arguments; the f32-row attention kinds only)."""
-        if rel_bias is not None and (not parity_attention_f32(self) or arena is not None or cross is not None):
-            raise K.VidilHipError("_run_layers_parity: rel_bias serves the f32-row self-attention of a stack without cross-attention or arena")
-        if cross_kv_len is not None:
-            raise K.VidilHipError("_run_layers_parity: cross_kv_len (masked cross-attention) is not built for the parity precision mode")
-        cfg = self.config
-        H, C = cfg.num_attention_heads, cfg.hidden_size
-        eps = cfg.layer_norm_eps
-        M = rows * T
-        dev, cdt = h32.device, h3.dtype
-        if ws is None:
-            ws = {}
-        q = ws.get("q")
-        if q is None or q.shape[0] < rows or q.shape[2] != T:
-            q = torch.empty((rows, H, T, 64), dtype=cdt, device=dev)
-            ws["q"] = q
-        o3 = torch.empty((M, 3 * C), dtype=cdt, device=dev)
-        tmp = torch.empty((M, C), dtype=torch.float32, device=dev)
-        inter3 = torch.empty((M, 3 * cfg.intermediate_size), dtype=cdt, device=dev)
-        # Which producers may leave the third plane of their [hi | lo | hi] rows unwritten (ADVICE r5): only those whose EVERY
-        # consumer takes the K-loop form of the compensated product, asked per CALL (K.split_k_serves).  inter3 feeds fc2 (f32
-        # epilogue); with the f32-row attention kinds h3 / o3 feed Q|K|V, the cross query, both output projections and fc1, all
-        # with the f32 epilogue; kind "16" feeds h3 to arena / short-sequence scatter epilogues, which run the plain K = 3 Kl
-        # product over all three planes.  The consumers state a_planes, so a launch that would read an unwritten plane fails
-        # (EINVAL) instead of computing on it.
-        f32_attn, arith = parity_attention_f32(self), parity_attention_arith(self)
-        qkv32 = torch.empty((M, 3 * C), dtype=torch.float32, device=dev) if f32_attn else None
-        q32 = torch.empty((M, C), dtype=torch.float32, device=dev) if f32_attn and cross is not None else None
-        d0 = p["layers"][0]
-        planes = planes_h = 3
-        if K.split_k_serves(inter3, d0["o_w3"], d0["o_b"], out=tmp, resid=h32):
-            planes = 2
-        if f32_attn and planes == 2 and all((
-                K.split_k_serves(h3, d0["qkv_w3"], d0["qkv_b"], out=qkv32),
-                K.split_k_serves(o3, d0["ao_w3"], d0["ao_b"], out=tmp, resid=h32),
-                K.split_k_serves(h3, d0["i_w3"], d0["i_b"], split3_out=inter3, act=K.ACT_GELU_ERF),
-                cross is None or K.split_k_serves(h3, d0["cq_w3"], d0["cq_b"], out=q32))):
-            planes_h = 2
-        K.poison_third_plane(planes, inter3)
-        K.poison_third_plane(planes_h, o3, h3)
-        ws["planes_h"] = planes_h
-        Nk = t_off + T
-        if arena is not None and T > 1 and t_off != 0:
-            raise K.VidilHipError("run_layers: a multi-token block can only be appended to a beam arena at position 0")
-        if f32_attn:
-            # Q | K | V (and the cross query) stay f32 and row-major, the KV arena and the cross K | V are f32:
-            # vidil_attention_f32 reads all of them in place.  (t_off > 0 happens in the arena form only.)
-            # (split-operand kind: the cross K | V of a decoder session are 16-bit fragment tiles instead)
-            kv16 = cross is not None and arith == 1 and cross.tiled and not getattr(cross, "f32", False)
-            if (arena is not None and arena.k.dtype != torch.float32) or (cross is not None and not getattr(cross, "f32", False) and not kv16):
-                raise K.VidilHipError("run_layers (parity mode, f32 attention): the KV arena / cross K|V of this session were built for "
-                                      "the 16-bit attention kernels — build the DecoderSession / CrossKV under the same $VIDIL_PARITY_ATTN")
-            if t_off != 0 and not (arena is not None and T == 1):
-                raise K.VidilHipError("run_layers (parity mode, f32 attention): cached self-attention keys are served by the arena form only")
-            if kv16 and T * max(1, cross_group) > 32 and cross_groups is None and cross_index is None:
-                # (ADVICE r5: the kv16 form serves at most 32 query rows per image — a DecoderSession's decode steps and shared
-                #  prompt pass; a longer prompt x group must be built with the f32-row cross K|V instead)
-                raise K.VidilHipError(f"run_layers (parity mode, split attention): {T} tokens x {cross_group} sequences per image exceed the 32 "
-                                      "query rows per image the 16-bit cross K/V tiles serve — build the session with tiled_cross=False")
-        for i, d in enumerate(p["layers"][:n_layers]):
-            if f32_attn:
-                K.gemm(h3, d["qkv_w3"], d["qkv_b"], out=qkv32, split_k=True, a_planes=planes_h)
-                if arena is not None and T == 1:
-                    arena.k[i][t_off].copy_(qkv32[:, C:2 * C])          # position t_off, slot = producing beam row
-                    arena.v[i][t_off].copy_(qkv32[:, 2 * C:])
-                    K.attention_f32(qkv32[:, :C], arena.k[i], arena.v[i], o3, Bq=rows, H=H, Nq=1, Nk=Nk, anc=arena.anc,
-                                    arena_rows=arena.rows, planes=planes_h)
-                else:
-                    K.attention_f32(qkv32[:, :C], qkv32[:, C:2 * C], qkv32[:, 2 * C:], o3, Bq=rows, H=H, Nq=T, Nk=T, causal=causal,
-                                    kv_len=kv_len, arith=arith, planes=planes_h, rel_bias=rel_bias, rel_off=rel_off)
-                    if arena is not None:   # the prompt's K / V in the arena: position t, slot r * arena_slot_stride
-                        blk = qkv32.view(rows, T, 3 * C)
-                        arena.k[i][:T, 0:rows * arena_slot_stride:arena_slot_stride] = blk[:, :, C:2 * C].permute(1, 0, 2)
-                        arena.v[i][:T, 0:rows * arena_slot_stride:arena_slot_stride] = blk[:, :, 2 * C:].permute(1, 0, 2)
-            elif arena is not None and T == 1:
-                K.gemm(h3, d["qkv_w3"], d["qkv_b"], split_k=True,
-                       arena=dict(q=q, k=arena.k[i], v=arena.v[i], T=1, H=H, part0=0, t_off=t_off, Tcap=arena.Tcap,
-                                  arena_rows=arena.rows, slot_stride=1, q_scale=0.125))
-                K.beam_attention(q, arena.k[i], arena.v[i], arena.anc, o3, rows=rows, H=H, n_keys=Nk, split3=True)
-            else:
-                K.gemm(h3, d["qkv_w3"], d["qkv_b"], split_k=True,
-                       heads=dict(q=q, k=self_k[i], vt=self_vt[i], T=T, H=H, part0=0, t_off=t_off, Tq_cap=T,
-                                  Tk_cap=Tk_cap, NP=NPs, q_scale=0.125))
-                K.attention(q, self_k[i], self_vt[i], o3, Bq=rows, H=H, Nq=T, Nk=Nk, Tq_cap=T, Tk_cap=Tk_cap, NP=NPs,
-                            causal=causal, causal_off=t_off, kv_len=kv_len, split3=True)
-                if arena is not None:
-                    K.gemm(h3, d["qkv_w3"][C:], d["qkv_b"][C:], split_k=True,
-                           arena=dict(k=arena.k[i], v=arena.v[i], T=T, H=H, part0=1, t_off=0, Tcap=arena.Tcap,
-                                      arena_rows=arena.rows, slot_stride=arena_slot_stride))
-            K.gemm(o3, d["ao_w3"], d["ao_b"], out=tmp, resid=h32, split_k=True, a_planes=planes_h)
-            K.layernorm(tmp, d["ao_g"], d["ao_bt"], eps, out16=h3, out32=h32, split3=True, planes=planes_h)
-            if cross is not None and f32_attn:
-                K.gemm(h3, d["cq_w3"], d["cq_b"], out=q32, split_k=True, a_planes=planes_h)
-                if kv16:
-                    for b0, b1 in self._cross_blocks(cross, cross_index, cross_groups):
-                        r0, r1 = (0, M) if (b0, b1) == (0, cross.B) else (b0 * cross_group * T, b1 * cross_group * T)
-                        K.attention_f32(q32[r0:r1], cross.k[i][b0:b1], cross.vt[i][b0:b1], o3[r0:r1], Bq=(r1 - r0) // T, H=H, Nq=T, Nk=cross.Te,
-                                        kv_rows=cross.Tk_cap, kv_group=cross_group, kv_index=cross_index, group_start=cross_groups,
-                                        max_group=cross_max_group, arith=1, kv16=True, planes=planes_h)
-                else:
-                    kv = cross.k[i]                                     # f32 [B, Te, 2C]: keys | values
-                    K.attention_f32(q32, kv[..., :C], kv[..., C:], o3, Bq=rows, H=H, Nq=T, Nk=cross.Te, kv_rows=cross.Te,
-                                    kv_group=cross_group, kv_index=cross_index, group_start=cross_groups, max_group=cross_max_group,
-                                    arith=arith, planes=planes_h)
-                K.gemm(o3, d["co_w3"], d["co_b"], out=tmp, resid=h32, split_k=True, a_planes=planes_h)
-                K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=h3, out32=h32, split3=True, planes=planes_h)
-            elif cross is not None:
-                K.gemm(h3, d["cq_w3"], d["cq_b"], heads=dict(q=q, T=T, H=H, part0=0, Tq_cap=T, q_scale=0.125), split_k=True)
-                # (project_cross_kv(last_layer_vt=True) keeps the LAST layer's values in a V^T buffer of their own)
-                last = i == len(p["layers"]) - 1 and cross.last_vt is not None
-                K.attention(q, cross.k[i], cross.last_vt if last else cross.vt[i], o3, Bq=rows, H=H, Nq=T, Nk=cross.Te, Tq_cap=T,
-                            Tk_cap=cross.Tk_cap, NP=cross.last_NP if last else cross.NP, kv_group=cross_group, kv_index=cross_index,
-                            group_start=cross_groups, max_group=cross_max_group, kv_tiled=cross.tiled, split3=True)
-                K.gemm(o3, d["co_w3"], d["co_b"], out=tmp, resid=h32, split_k=True)
-                K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=h3, out32=h32, split3=True, planes=planes_h)
-            K.gemm(h3, d["i_w3"], d["i_b"], split3_out=inter3, act=K.ACT_GELU_ERF, split_k=True, split3_planes=planes, a_planes=planes_h)
-            K.gemm(inter3, d["o_w3"], d["o_b"], out=tmp, resid=h32, split_k=True, a_planes=planes)
-            K.layernorm(tmp, d["o_g"], d["o_bt"], eps, out16=h3, out32=h32, split3=True, planes=planes_h)
-        return h32, h3
-
     def _text_fold_ok(self, cdt):
         C = self.config.hidden_size
         return (os.environ.get("VIDIL_FUSE_LN", "1") != "0" and C % 64 == 0 and C <= 1024
                 and cdt in (torch.float16, torch.bfloat16))
 
-    def _run_layers_fused(self, h32, h16, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len, cross, cross_index=None,
-                          cross_group=1, cross_groups=None, cross_max_group=0, n_layers=None, self_done_first=False,
-                          stop_after_self=False, state_in=None, arena: "BeamArena" = None, arena_slot_stride=1, cross_kv_len=None,
+    def decoder_fused_ln(self, cdt):
+        """Whether the decoder passes over this trunk (a DecoderSession's, ``causal_pass``) run the LN-folded stack: a property of
+        the model and $VIDIL_DECODE_FUSE_LN (=0: the unfused launches), never of a batch."""
+        return (os.environ.get("VIDIL_DECODE_FUSE_LN", "1") != "0" and not self.parity and self._text_fold_ok(cdt)
+                and self.config.add_cross_attention)
+
+    def scratch_kv(self, rows, T, cdt, dev):
+        """The self-attention K [rows,H,T,64] / V^T [rows,H,64,NPs] of ONE layer, presented as [L][...] to ``run_layers``: a block
+        that attends to itself keeps no cache, so every layer reuses the pair.  Returns (k, vt, NPs)."""
+        H, L = self.config.num_attention_heads, self.config.num_hidden_layers
+        NPs = (T + 15) // 16 * 16
+        k = torch.empty((1, rows, H, T, 64), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
+        vt = torch.empty((1, rows, H, 64, NPs), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
+        return k, vt, NPs
+
+    def _run_layers_fused(self, h32, h16, *, rows, T, self_k, self_vt, t_off, Tk_cap, NPs, causal, kv_len, route=None, n_layers=None,
+                          self_done_first=False, stop_after_self=False, state_in=None, arena: "BeamArena" = None, arena_slot_stride=1,
                           arena_prompt=False, hidden_out=None):
         """run_layers for encoder batches with cross-attention, WITHOUT LayerNorm launches between the GEMMs
         (models/med.py:236-239,306-317 are post-LN: h = LN(x + dense(.)) is the next dense's input AND the next residual).
@@ -758,9 +797,6 @@ class BertModel(PackedCache, nn.Module):
             wf, bf, cs = fw[i][name]
             return K.gemm(h16, wf, bf, ln=(cs, eps, stats[cur]), **kw)
 
-        if arena is not None and T > 1 and t_off != 0:
-            raise K.VidilHipError("run_layers: a multi-token block can only be appended to a beam arena at position 0")
-
         def arena_kv(i, d):
             """the prompt block's K | V once more, in the arena layout (a prompt is a few tokens): the K|V rows of the same
             (folded) weights — same values as the per-head K / V the block attends to"""
@@ -771,9 +807,7 @@ class BertModel(PackedCache, nn.Module):
             wf, bf, cs = fw[i]["qkv"]
             return K.gemm(h16, wf[C:], bf[C:], ln=(cs[C:], eps, stats[cur]), **kw)
 
-        ckl = self._cross_len_arg(cross_kv_len, rows)
-        layers = p["layers"][:n_layers]
-        for i, d in enumerate(layers):
+        for i, d in enumerate(p["layers"][:n_layers]):
             if self_done_first and i == 0:
                 pass
             elif arena is not None and T == 1 and not arena_prompt:
@@ -794,12 +828,7 @@ class BertModel(PackedCache, nn.Module):
             if stop_after_self:
                 return h32, h16, stats[cur], pend
             consumer("cq", i, d["cq_w"], d["cq_b"], heads=dict(q=q, T=T, H=H, part0=0, Tq_cap=T, q_scale=0.125))
-            mg = self._cross_bound(cross, T, cross_index, cross_group, cross_groups, cross_max_group)
-            for b0, b1 in self._cross_blocks(cross, cross_index, cross_groups):
-                r0, r1 = (0, rows) if (b0, b1) == (0, cross.B) else (b0 * cross_group, b1 * cross_group)
-                K.attention(q[r0:r1], cross.k[i][b0:b1], cross.vt[i][b0:b1], o[r0 * T:r1 * T], Bq=r1 - r0, H=H, Nq=T, Nk=cross.Te,
-                            Tq_cap=T, Tk_cap=cross.Tk_cap, NP=cross.NP, kv_group=cross_group, kv_index=cross_index,
-                            group_start=cross_groups, max_group=mg, kv_tiled=self._cross_tiled(cross), **ckl(r0, r1))
+            route.attend(i, q, o, T)
             residual_gemm(o, d["co_w"], d["co_b"], d["co_g"], d["co_bt"])
             consumer("fc1", i, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
             residual_gemm(inter, d["o_w"], d["o_b"], d["o_g"], d["o_bt"])
@@ -840,14 +869,7 @@ class BertModel(PackedCache, nn.Module):
     def bidirectional_pass(self, h32, h16, P, T, kv_len_i32, cross, *, hidden_out=None, **cross_kw):
         """The stack pass of ``encode`` on embedded rows (h32, h16) [P*T, C], updated in place: every token attends to the first
         kv_len[p] tokens of its sequence and to ``cross`` (cross_kw: cross_index / cross_groups / cross_max_group / cross_kv_len)."""
-        H = self.config.num_attention_heads
-        L = self.config.num_hidden_layers
-        dev = h32.device
-        NPs = (T + 15) // 16 * 16
-        cdt = h16.dtype
-        sk = torch.empty((1, P, H, T, 64), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
-        sv = torch.empty((1, P, H, 64, NPs), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
-        # (one scratch K / V^T buffer is reused by every layer: the encoder keeps no cache)
+        sk, sv, NPs = self.scratch_kv(P, T, h16.dtype, h32.device)
         self.run_layers(h32, h16, rows=P, T=T, self_k=sk, self_vt=sv, t_off=0, Tk_cap=T, NPs=NPs, causal=False,
                         kv_len=kv_len_i32, cross=cross, hidden_out=hidden_out, **cross_kw)
         return h32, h16
@@ -859,17 +881,9 @@ class BertModel(PackedCache, nn.Module):
         cross_kv_len).  The stack is the one a DecoderSession runs (LN-folded or parity) — never a function of the batch.
         kv_len (i32 [rows], device): a row also ignores the keys past kv_len[r] (models/med.py:651, causal x padding mask);
         a query inside its sequence sees the same keys with and without it."""
-        cfg = self.config
-        H, L = cfg.num_attention_heads, cfg.num_hidden_layers
-        dev = h32.device
-        cdt = h16.dtype
-        fused = (os.environ.get("VIDIL_DECODE_FUSE_LN", "1") != "0" and not self.parity and self._text_fold_ok(cdt)
-                 and cfg.add_cross_attention and cross is not None)
-        NPs = (T + 15) // 16 * 16
-        sk = torch.empty((1, rows, H, T, 64), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
-        sv = torch.empty((1, rows, H, 64, NPs), dtype=cdt, device=dev).expand(L, -1, -1, -1, -1)
+        sk, sv, NPs = self.scratch_kv(rows, T, h16.dtype, h32.device)
         self.run_layers(h32, h16, rows=rows, T=T, self_k=sk, self_vt=sv, t_off=0, Tk_cap=T, NPs=NPs, causal=True, kv_len=kv_len,
-                        cross=cross, fused=fused, hidden_out=hidden_out, **cross_kw)
+                        cross=cross, fused=self.decoder_fused_ln(h16.dtype) and cross is not None, hidden_out=hidden_out, **cross_kw)
         return h32, h16
 
     def encode_cls(self, ids_i32, kv_len_i32, cross: CrossKV, cross_index=None, cross_groups=None, cross_max_group=0,
@@ -895,29 +909,22 @@ class BertModel(PackedCache, nn.Module):
         eps = cfg.layer_norm_eps
         dev = ids_i32.device
         cdt = p["layers"][0]["qkv_w"].dtype
-        NPs = (T + 15) // 16 * 16
         if cross is not None and cross.NP == 0 and cross.last_vt is None:
             raise K.VidilHipError("encode_cls: row-major cross values need project_cross_kv(last_layer_vt=True)")
-
-        def scratch(rows):
-            k = torch.empty((rows, H, T, 64), dtype=cdt, device=dev)
-            v = torch.empty((rows, H, 64, NPs), dtype=cdt, device=dev)
-            return k, v, k.unsqueeze(0).expand(L, -1, -1, -1, -1), v.unsqueeze(0).expand(L, -1, -1, -1, -1)
-
         h32, h16 = self.embed(ids_i32.reshape(-1), T, 0)
         shared = pair_text is not None and cross is not None and L > 1
         fold = self._text_fold_ok(cdt) and cross is not None and L > 1
         state = None
         if shared:
             U = ids_i32.shape[0]
-            _, _, uk, uv = scratch(U)
-            kw = dict(rows=U, T=T, self_k=uk, self_vt=uv, t_off=0, Tk_cap=T, NPs=NPs, causal=False, kv_len=kv_len_i32, cross=None,
-                      n_layers=1, stop_after_self=True)
+            uk, uv, NPs = self.scratch_kv(U, T, cdt, dev)
+            kw = dict(rows=U, T=T, self_k=uk, self_vt=uv, t_off=0, Tk_cap=T, NPs=NPs, causal=False, kv_len=kv_len_i32, n_layers=1,
+                      stop_after_self=True)
             if fold:     # the text-only front leaves the raw sum + partials, exactly as the expanded batch's layer 0 would
                 h32, h16, st0, pend0 = self._run_layers_fused(h32, h16, **kw)
                 state = (st0.view(U, T, -1).index_select(0, pair_text).view(-1, st0.shape[1], 2).contiguous(), pend0)
             else:
-                self.run_layers(h32, h16, **kw)
+                self.run_layers(h32, h16, cross=None, **kw)
             h32 = h32.view(U, T, C).index_select(0, pair_text).view(-1, C)
             h16 = h16.view(U, T, C).index_select(0, pair_text).view(-1, C)
             kv_len_i32 = kv_len_i32.index_select(0, pair_text).contiguous()
@@ -926,14 +933,15 @@ class BertModel(PackedCache, nn.Module):
             h16 = h16.view(-1, T, C).index_select(0, pair_text).view(-1, C)
             kv_len_i32 = kv_len_i32.index_select(0, pair_text).contiguous()
         P = h32.shape[0] // T
-        sk, sv, sk_l, sv_l = scratch(P)
-        kw = dict(rows=P, T=T, self_k=sk_l, self_vt=sv_l, t_off=0, Tk_cap=T, NPs=NPs, causal=False, kv_len=kv_len_i32, cross=cross,
-                  cross_index=cross_index, cross_groups=cross_groups, cross_max_group=cross_max_group, n_layers=L - 1,
-                  self_done_first=shared)
+        sk_l, sv_l, NPs = self.scratch_kv(P, T, cdt, dev)
+        sk, sv = sk_l[0], sv_l[0]
+        route = CrossRoute(self, cross, P, index=cross_index, groups=cross_groups, max_group=cross_max_group)
+        kw = dict(rows=P, T=T, self_k=sk_l, self_vt=sv_l, t_off=0, Tk_cap=T, NPs=NPs, causal=False, kv_len=kv_len_i32, route=route,
+                  n_layers=L - 1, self_done_first=shared)
         if state is not None:
             self._run_layers_fused(h32, h16, state_in=state, **kw)
         else:
-            self.run_layers(h32, h16, **kw)
+            self.run_layers(h32, h16, cross=cross, **kw)
         d = p["layers"][L - 1]
         q1 = torch.empty((P, H, 1, 64), dtype=cdt, device=dev)
         o1 = torch.empty((P, C), dtype=cdt, device=dev)
@@ -953,8 +961,7 @@ class BertModel(PackedCache, nn.Module):
             K.gemm(c16, d["cq_w"], d["cq_b"], heads=dict(q=q1, T=1, H=H, part0=0, Tq_cap=1, q_scale=0.125))
             # (over LONG_KEYS encoder states: the bound becomes max(max_group, 33) — one query row per pair)
             K.attention(q1, cross.k[L - 1], vt, o1, Bq=P, H=H, Nq=1, Nk=cross.Te, Tq_cap=1, Tk_cap=cross.Te, NP=NP,
-                        kv_index=cross_index, group_start=cross_groups,
-                        max_group=self._cross_bound(cross, 1, cross_index, 1, cross_groups, cross_max_group))
+                        kv_index=route.index, group_start=route.groups, max_group=route.bound(1))
             K.gemm(o1, d["co_w"], d["co_b"], out=tmp, resid=c32)
             K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=c16, out32=c32)
         inter = K.gemm(c16, d["i_w"], d["i_b"], act=K.ACT_GELU_ERF)
@@ -966,11 +973,11 @@ class BertModel(PackedCache, nn.Module):
         """encode_cls_parity serves this model and these cross K / V: the parity mode with an f32-row attention kind (cross K | V
         as f32 rows: project_cross_kv's parity form) and more than one layer."""
         return (self.parity and parity_attention_f32(self) and self.config.num_hidden_layers > 1
-                and (cross is None or getattr(cross, "f32", False)))
+                and (cross is None or cross.f32))
 
     def encode_cls_parity(self, ids_i32, kv_len_i32, cross: CrossKV, cross_index=None, cross_groups=None, cross_max_group=0):
         """encode_cls in the parity precision mode (f32-row attention kinds; cls_last_parity_ok): layers 0..L-2 on every token
-        (_run_layers_parity), the last layer's keys / values of the self-attention over every token, and everything else of that
+        (parity_layers), the last layer's keys / values of the self-attention over every token, and everything else of that
         layer — the query, both attentions, the three dense + LayerNorm blocks and the feed-forward — on the P [CLS] rows alone.
         Same operands per [CLS] row as encode(); the one-row self-attention is vidil_attention_f32's one-row-per-unit form.
         Returns (c32 f32 [P, C], c3 [P, 3C] = its [hi | lo | hi] rows)."""
@@ -988,9 +995,8 @@ class BertModel(PackedCache, nn.Module):
         h32, h3 = self.embed(ids_i32.reshape(-1), T, 0)
         cdt = h3.dtype
         ws = {}
-        self._run_layers_parity(p, h32, h3, rows=P, T=T, self_k=None, self_vt=None, t_off=0, Tk_cap=T, NPs=0, causal=False,
-                                kv_len=kv_len_i32, cross=cross, cross_index=cross_index, cross_group=1, cross_groups=cross_groups,
-                                cross_max_group=cross_max_group, ws=ws, arena=None, arena_slot_stride=1, n_layers=L - 1)
+        route = CrossRoute(self, cross, P, index=cross_index, groups=cross_groups, max_group=cross_max_group)
+        parity_layers(self, p, h32, h3, rows=P, T=T, causal=False, kv_len=kv_len_i32, route=route, ws=ws, n_layers=L - 1)
         planes_h = ws["planes_h"]            # (planes of h3 the last LayerNorm wrote; the [CLS] side below writes all three)
         d = p["layers"][L - 1]
         kv32 = torch.empty((P * T, 2 * C), dtype=torch.float32, device=dev)
@@ -1007,8 +1013,8 @@ class BertModel(PackedCache, nn.Module):
         if cross is not None:
             K.gemm(c3, d["cq_w3"], d["cq_b"], out=q32, split_k=True)
             kv = cross.k[L - 1]                                     # f32 [B, Te, 2C]: keys | values
-            K.attention_f32(q32, kv[..., :C], kv[..., C:], o3, Bq=P, H=H, Nq=1, Nk=cross.Te, kv_rows=cross.Te, kv_index=cross_index,
-                            group_start=cross_groups, max_group=cross_max_group, arith=arith)
+            K.attention_f32(q32, kv[..., :C], kv[..., C:], o3, Bq=P, H=H, Nq=1, Nk=cross.Te, kv_rows=cross.Te, kv_index=route.index,
+                            group_start=route.groups, max_group=route.max_group, arith=arith)
             K.gemm(o3, d["co_w3"], d["co_b"], out=tmp, resid=c32, split_k=True)
             K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=c3, out32=c32, split3=True)
         inter3 = torch.empty((P, 3 * cfg.intermediate_size), dtype=cdt, device=dev)

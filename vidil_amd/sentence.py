@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from . import kernels as K
-from .med import BertModel
+from .med import parity_layers
 from .packing import PackedCache, require_cuda, set_parity_attention, v32, w3
 from .tokenizer import init_sentence_tokenizer
 
@@ -176,10 +176,7 @@ class SentenceEncoder(PackedCache, nn.Module):
         K.layernorm(raw, p["emb_g"], p["emb_b"], cfg.layer_norm_eps, out16=h3, out32=h32, split3=True)
         # the parity layer sequence of the MED text stack without cross-attention — Q|K|V -> attention_f32 -> output GEMM +
         # residual -> LN -> fc1 + GELU -> fc2 + residual -> LN —, its self-attention with this model's bias table
-        BertModel._run_layers_parity(self, p, h32, h3, rows=B, T=T, self_k=None, self_vt=None, t_off=0, Tk_cap=T, NPs=0, causal=False,
-                                     kv_len=lens_i32, cross=None, cross_index=None, cross_group=1, cross_groups=None,
-                                     cross_max_group=0, ws=None, arena=None, arena_slot_stride=1,
-                                     rel_bias=p["rel_bias"], rel_off=p["rel_off"])
+        parity_layers(self, p, h32, h3, rows=B, T=T, causal=False, kv_len=lens_i32, rel_bias=p["rel_bias"], rel_off=p["rel_off"])
         return h32
 
     @torch.no_grad()
