@@ -458,7 +458,7 @@ class BertModel(PackedCache, nn.Module):
         p = dict(word=v32(e.word_embeddings.weight).view(self.config.vocab_size, -1),
                  pos=v32(e.position_embeddings.weight).view(self.config.max_position_embeddings, -1),
                  emb_g=v32(e.LayerNorm.weight), emb_b=v32(e.LayerNorm.bias), layers=[])
-        for l in self.encoder.layer:
+        for i, l in enumerate(self.encoder.layer):
             a, o = l.attention.self, l.attention.output
             d = dict(qkv_w=w16(a.query.weight, a.key.weight, a.value.weight, dtype=c),
                      qkv_b=v32(a.query.bias, a.key.bias, a.value.bias),
@@ -468,22 +468,28 @@ class BertModel(PackedCache, nn.Module):
                      o_w=w16(l.output.dense.weight, dtype=c), o_b=v32(l.output.dense.bias),
                      o_g=v32(l.output.LayerNorm.weight), o_bt=v32(l.output.LayerNorm.bias))
             if hasattr(l, "crossattention"):
-                ca, co = l.crossattention.self, l.crossattention.output
-                d.update(cq_w=w16(ca.query.weight, dtype=c), cq_b=v32(ca.query.bias),
-                         ckv_w=w16(ca.key.weight, ca.value.weight, dtype=c), ckv_b=v32(ca.key.bias, ca.value.bias),
-                         co_w=w16(co.dense.weight, dtype=c), co_b=v32(co.dense.bias),
-                         co_g=v32(co.LayerNorm.weight), co_bt=v32(co.LayerNorm.bias))
-                if self.fp8:     # fp8 tower mode: the image-side K|V projection (its A rows are a tower's output) on e4m3 too
-                    d["ckv_w8"], d["ckv_s"] = w8(ca.key.weight, ca.value.weight)
+                self._pack_cross(i, l.crossattention, d)
             if self.parity:      # parity precision mode: [W_hi | W_hi | W_lo] for every GEMM of the stack
                 d.update(qkv_w3=w3(a.query.weight, a.key.weight, a.value.weight, dtype=c), ao_w3=w3(o.dense.weight, dtype=c),
                          i_w3=w3(l.intermediate.dense.weight, dtype=c), o_w3=w3(l.output.dense.weight, dtype=c))
-                if hasattr(l, "crossattention"):
-                    d.update(cq_w3=w3(ca.query.weight, dtype=c), ckv_w3=w3(ca.key.weight, ca.value.weight, dtype=c),
-                             co_w3=w3(co.dense.weight, dtype=c))
             p["layers"].append(d)
         p["parity"] = self.parity
         return p
+
+    def _pack_cross(self, i, x, d):
+        """The operands of layer i's cross-attention block ``x`` into the layer's dict ``d`` (nlvr_encoder.BertModel overrides it
+        with the twin block's)."""
+        c = self.cdt
+        ca, co = x.self, x.output
+        d.update(cq_w=w16(ca.query.weight, dtype=c), cq_b=v32(ca.query.bias),
+                 ckv_w=w16(ca.key.weight, ca.value.weight, dtype=c), ckv_b=v32(ca.key.bias, ca.value.bias),
+                 co_w=w16(co.dense.weight, dtype=c), co_b=v32(co.dense.bias),
+                 co_g=v32(co.LayerNorm.weight), co_bt=v32(co.LayerNorm.bias))
+        if self.fp8:     # fp8 tower mode: the image-side K|V projection (its A rows are a tower's output) on e4m3 too
+            d["ckv_w8"], d["ckv_s"] = w8(ca.key.weight, ca.value.weight)
+        if self.parity:
+            d.update(cq_w3=w3(ca.query.weight, dtype=c), ckv_w3=w3(ca.key.weight, ca.value.weight, dtype=c),
+                     co_w3=w3(co.dense.weight, dtype=c))
 
     def pack_flags(self):
         # (the attention kind of the parity mode decides the dtype of a session's KV arena and cross K|V: a change re-packs, and
@@ -709,16 +715,23 @@ class BertModel(PackedCache, nn.Module):
             if stop_after_self:
                 break
             if cross is not None:
-                K.gemm(h16, d["cq_w"], d["cq_b"], heads=dict(q=q, T=T, H=H, part0=0, Tq_cap=T, q_scale=0.125))
-                route.attend(i, q, o, T)
-                K.gemm(o, d["co_w"], d["co_b"], out=tmp, resid=h32)
-                K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=h16, out32=h32)
+                self.cross_block(i, d, route, q, o, tmp, h32, h16, T)
             K.gemm(h16, d["i_w"], d["i_b"], out=inter, act=K.ACT_GELU_ERF)
             K.gemm(inter, d["o_w"], d["o_b"], out=tmp, resid=h32)
             K.layernorm(tmp, d["o_g"], d["o_bt"], eps, out16=h16, out32=h32)
             if hidden_out is not None:
                 hidden_out.append(h32.clone())
         return h32, h16
+
+    def cross_block(self, i, d, route, q, o, tmp, h32, h16, T):
+        """The cross-attention block of layer i on the plain unfused path of ``run_layers`` (models/med.py:228-239 with encoder
+        states): query, the route's attention launches, dense + residual, LayerNorm — on run_layers' scratch (q, o, tmp).
+        nlvr_encoder.BertModel overrides it with the twin block."""
+        H, eps = self.config.num_attention_heads, self.config.layer_norm_eps
+        K.gemm(h16, d["cq_w"], d["cq_b"], heads=dict(q=q, T=T, H=H, part0=0, Tq_cap=T, q_scale=0.125))
+        route.attend(i, q, o, T)
+        K.gemm(o, d["co_w"], d["co_b"], out=tmp, resid=h32)
+        K.layernorm(tmp, d["co_g"], d["co_bt"], eps, out16=h16, out32=h32)
 
     #: vidil_attention's short kernels end here; past it the long-key form serves MORE than 32 query rows per unit on plain K / V,
     #: the key-split form at most 32 on fragment tiles (a decoder session's: kv_tiled = 2)
