@@ -421,6 +421,13 @@ int vidil_l2_normalize_rows(float* x, int32_t n, int32_t D, void* stream);
 /* of an image are still identical and only beam 0 (score 0; the others carry */
 /* -1e9 and can never reach the top 2nb) was run through the decoder.         */
 /* out_scores f32 [B, 2nb], out_index i32 [B, 2nb] (flat index beam*V+tok).   */
+/* nb = 1..16 (more: VIDIL_EUNSUP).  1..4 run a kernel that keeps sorted       */
+/* candidate lists in registers, 5..16 one that streams candidates through a  */
+/* per-wave LDS buffer; same contract, every logits row is read once by both. */
+/* For nb >= 5 a launch with nbl*V < 2*nb candidates is VIDIL_EINVAL (HF's     */
+/* topk fails there too); for nb <= 4 the missing places hold -inf/0x7fffffff.*/
+/* For nb >= 5 logits that are not device memory are VIDIL_EUNSUP (no host    */
+/* path), found by one runtime query before the launch.                       */
 int vidil_logsoftmax_topk(const float* logits, const float* beam_scores,
                           int32_t B, int32_t nb, int32_t beams_in_logits,
                           int32_t V, int32_t ban_token, float* out_scores,
@@ -434,6 +441,7 @@ int vidil_logsoftmax_topk(const float* logits, const float* beam_scores,
 /* ids of the row's sequence seqs[(b*nb+beam)*ld_seqs ..] (prompt included):       */
 /*   lp[t] = lp[t] < 0 ? lp[t] * penalty : lp[t] / penalty   (f32, once per token) */
 /* before the ban (MinLength) and the beam score are applied.  cur_len <= 64.      */
+/* nb = 1..16 as for vidil_logsoftmax_topk (the same two kernels' penalty forms).  */
 /*                                                                                 */
 /* nb == 0: the TEACHER-FORCED form — no search, score the given token (reference: */
 /* models/med.py:909-917, the cross-entropy of BertLMHeadModel.forward(labels=...)).*/
@@ -488,6 +496,7 @@ typedef struct vidil_beam_state {
 
 /* BeamSearchScorer.process: walk the 2*nb candidates, bank EOS hypotheses,   */
 /* fill the next beams, update done flags; then append tokens into seqs_next. */
+/* nb = 1..16, max_len <= 64 (also for vidil_beam_finalize).                  */
 int vidil_beam_update(const vidil_beam_state* st, const float* cand_scores,
                       const int32_t* cand_index, int32_t B, int32_t nb,
                       int32_t V, int32_t cur_len, int32_t max_len,

@@ -270,6 +270,7 @@ class BLIP_Decoder(nn.Module):
         selection of every step penalises the log-probabilities of the tokens a beam already holds, prompt included
         (``vidil_logsoftmax_topk_penalty``; oracle/beam_ref.py ``repetition_penalty``)."""
         require_cuda(enc16, "BLIP_Decoder.generate")
+        K.require_num_beams(num_beams, "generate")          # (1..K.MAX_BEAMS; refused here, not in the middle of a search)
         if not repetition_penalty > 0:
             raise ValueError(f"repetition_penalty must be a strictly positive float, got {repetition_penalty}")   # (HF's message)
         kw = dict(num_beams=num_beams, max_length=max_length, min_length=min_length, check_done_every=check_done_every,
@@ -561,6 +562,7 @@ class BLIP_Decoder(nn.Module):
             _, y16 = self.visual_encoder.forward_both(image)
             return self.decode_captions(self.sample_ids(y16, image.shape[0], top_p=top_p, max_length=max_length,
                                                         min_length=min_length))
+        K.require_num_beams(num_beams, "BLIP_Decoder.generate")              # (before the ViT runs)
         _, y16 = self.visual_encoder.forward_both(image)
         out_tok, _ = self.generate_ids(y16, image.shape[0], num_beams=num_beams, max_length=max_length,
                                        min_length=min_length, repetition_penalty=repetition_penalty)
@@ -705,6 +707,8 @@ class BLIP_Video_Decoder(BLIP_Decoder):
         falls in (``sample=True``: one ``seed`` for the call — default: a fresh one, as sample_ids draws it — and the video's
         index in the call as its Philox row).  ``details`` (dict, optional; what the tests compare): receives ``tokens`` i32
         [B, max_length] on the host."""
+        if not sample:
+            K.require_num_beams(num_beams, "BLIP_Video_Decoder.generate")   # (before the ViT runs)
         tok16, B = self._tokens(video)
         if sample and seed is None:
             self._sample_calls = getattr(self, "_sample_calls", 0) + 1

@@ -204,6 +204,8 @@ class BLIP_VQA(nn.Module):
         self._require_plain()
         if not train and inference not in ("generate", "rank"):
             raise ValueError(f"unknown inference {inference!r} (generate | rank)")
+        if not train and inference == "generate":
+            K.require_num_beams(VQA_NUM_BEAMS, "BLIP_VQA generate")          # (before the ViT runs)
         Q = image.shape[0]
         _, y16 = self.visual_encoder.forward_both(image)
         ids, lens = self.tokenize_questions(question)
@@ -324,6 +326,8 @@ class BLIP_Video_VQA(BLIP_VQA):
         arange(B) of ``question_states_grouped``."""
         if not train and inference not in ("generate", "rank"):
             raise ValueError(f"unknown inference {inference!r} (generate | rank)")
+        if not train and inference == "generate":
+            K.require_num_beams(VQA_NUM_BEAMS, "BLIP_Video_VQA generate")    # (before the ViT runs)
         B = video.shape[0]
         ids, lens = self.tokenize_questions(question)
         if ids.shape[0] != B:

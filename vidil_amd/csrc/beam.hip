@@ -8,16 +8,21 @@
 //                     pass per row: online max / sum of exponentials),
 //                     optional EOS ban, + beam score, sorted top-2nb over
 //                     nb*V candidates (ties -> lower flat index).
-//   beam_update     : one thread per image; BeamSearchScorer.process + the
-//                     input_ids gather/append.
+//                     nb 1..4: lsm_topk_kernel<NB, RP>, sorted candidate lists in
+//                     registers.  nb 5..16: lsm_topk_wide_kernel<RP>, a streaming
+//                     selection through a per-wave LDS buffer (same contract,
+//                     nb a run-time argument).
+//   beam_update     : BeamSearchScorer.process + the input_ids gather/append; one
+//                     thread per image for nb <= 4, one wave per image (lane 0
+//                     keeps the books, 64 lanes copy the tokens) for nb 5..16.
 //   beam_finalize   : one thread per image; BeamSearchScorer.finalize.
 #include <math.h>
 #include "common.h"
 
 namespace {
 
-constexpr int MAXC = 8;   // 2*nb candidates, nb <= 4
-constexpr int MAXNB = 4;
+constexpr int MAXNB = 4;        // widest search of the register-list selection kernel and the thread-per-image update
+constexpr int MAXNB_WIDE = 16;  // widest search at all
 constexpr int MAXLEN = 64;
 
 struct Cand {
@@ -219,6 +224,312 @@ __global__ __launch_bounds__(256) void lsm_topk_kernel(const float* __restrict__
   }
 }
 
+// ---- wide selection: 5 <= nb <= 16 (K = 2 nb up to 32).  The register lists of lsm_topk_kernel do not stretch that far (two
+// sorted K-lists per thread, 256 * K * 8 bytes of LDS), so this kernel keeps NO per-thread list.  Same contract, same single read
+// of every row, same online softmax per thread; nb is a run-time argument.
+//
+//   buffer   Every wave owns WCAP cells (value, index) in LDS.  Cells [0, ic) hold candidates of the image from earlier rows as
+//            (score, flat index); cells [ic, cnt) hold candidates of the row being read as (logit, index in the row).
+//   stream   An element at or above the wave's bound `thr` (-inf at the start of a row) that is neither banned nor in the row's
+//            history is appended by ballot compaction: position = cnt + number of appending lanes below this one.
+//   reduce   When cnt passes WCAP - 64 the wave reduces the row's cells: every lane takes the largest of its (up to) WPL cells,
+//            and `t` is the K-th largest of those 64 lane maxima (rank by counting over 64 lane broadcasts).  The maxima are 64
+//            DISTINCT elements of the row, so t is a lower bound of the row's K-th best logit; thr = t minus the margin of the
+//            narrow kernel (far wider than any pair of logits whose rounded scores could tie), and the cells below thr are
+//            compacted away.  An element below thr has K elements of the row whose SCORES are strictly greater, so it is in no
+//            top K: dropping it changes no output.  (On Gaussian logits the 32nd largest of 64 maxima of 8 is about the 42nd of
+//            512: the cells shrink to ~1/12 and fill up again about twice in a row of 30,524.)
+//   bounded  Appends happen only while cnt <= WCAP - 64 and add at most 64.  A reduce leaves at most WCAP / 2 cells of the row, or
+//            else (more than that within the margin of t: rows of near-equal logits) the wave switches to the STRICT form for the
+//            rest of the row: the row's cells are cut to their exact best K in (logit descending, index ascending) order by K
+//            rounds of a wave-wide arg-max, and only elements better than the K-th in that order are appended from then on.  That
+//            is the order the narrow kernel's per-thread lists keep, and what equal logits need (equal logits give equal scores,
+//            the lower index wins); it is the one place where two DIFFERENT logits whose rounded scores tie are ordered by logit.
+//            A row starts with ic <= WKEEP cells of the image, so cnt <= WKEEP + WCAP / 2 after a reduce.  NaN compares false
+//            against every bound, so a NaN never enters a buffer; every loop has a trip count fixed by V, K or WCAP.
+//   row end  The block combines the threads' softmax states into (max, log-sum-exp) as the narrow kernel does; every wave turns
+//            the row's cells into scores `(x - max) - lse + beam_score` in place and, in the penalty form, appends the history
+//            tokens (one per thread, scored as in the narrow kernel).  All cells are candidates of the image now.  With more than
+//            WKEEP of them the wave prunes: the K-th largest lane maximum of the SCORES bounds the image's K-th best score from
+//            below, cells under it have K strictly better ones; should more than WKEEP tie or pass (not seen on real logits), the
+//            exact best K in (score descending, flat index ascending) order are kept.  No margin: these are the final keys.
+//   merge    After the last row every wave selects its exact best K (K rounds of arg-max over its cells), the four lists meet
+//            in LDS, wave 0 selects the image's K best and lane r writes place r.
+//
+// All loops over a row have the same trip count in every lane (a lane past the end of the row carries a false predicate), because
+// reduce and the selections shuffle across the wave.
+constexpr int WCAP = 512;           // cells per wave
+constexpr int WPL = WCAP / 64;      // cells per lane
+constexpr int WKEEP = 128;          // cells of the image a wave takes into the next row at most
+constexpr int WMAXK = 2 * MAXNB_WIDE;
+
+__device__ __forceinline__ void wave_lds_sync() {   // LDS written by some lanes of a wave is read by others: no instruction,
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (a wave's LDS operations execute in order) but the compiler
+  __builtin_amdgcn_wave_barrier();                         // must not move accesses across this point
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ int lanes_below(unsigned long long bal) {   // set bits of `bal` below this lane
+  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+}
+// K-th largest (1 <= K <= 64, with multiplicity) of the 64 lanes' values; no NaN among them.
+__device__ __forceinline__ float lanes_kth_largest(float v, int K) {
+  int above = 0;
+#pragma unroll
+  for (int l = 0; l < 64; ++l)
+    above += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)) > v ? 1 : 0;
+  // the values with fewer than K values above them are the K largest: their smallest is the K-th
+  return -wave_max(above < K ? -v : -INFINITY);
+}
+// The best K (<= 64) of the wave's 64 * N cells in (s descending, i ascending) order: lane r returns the r-th, every other lane
+// (and every place past the number of cells) the empty cell (-inf, 0x7fffffff).  Empty cells are never chosen; indices are unique.
+// The cells are consumed.  All 64 lanes must call it.
+template <int N>
+__device__ __forceinline__ Cand select_k(float (&s)[N], int (&x)[N], int K) {
+  const int lane = threadIdx.x & 63;
+  Cand mine{-INFINITY, 0x7fffffff};
+  for (int r = 0; r < K; ++r) {
+    Cand c{-INFINITY, 0x7fffffff};
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if (better(s[j], x[j], c.s, c.i)) { c.s = s[j]; c.i = x[j]; }
+    c = wave_best(c);
+    if (c.i == 0x7fffffff) break;                      // (wave-uniform) nothing left
+    if (lane == r) mine = c;
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if (x[j] == c.i) { s[j] = -INFINITY; x[j] = 0x7fffffff; }
+  }
+  return mine;
+}
+
+template <bool RP>
+__global__ __launch_bounds__(256) void lsm_topk_wide_kernel(const float* __restrict__ logits,
+                                                            const float* __restrict__ beam_scores, int NB, int NBL, int V,
+                                                            int ban, float* __restrict__ out_s, int* __restrict__ out_i,
+                                                            const int32_t* __restrict__ hist, int hist_len, int ld_hist,
+                                                            float penalty) {
+  __shared__ float red[4];
+  __shared__ int hs_tok[MAXLEN];
+  __shared__ unsigned hs_bits[256];                      // penalty form: 8,192-bit filter in front of the history list
+  __shared__ float buf_x[4 * WCAP];
+  __shared__ int buf_i[4 * WCAP];
+  __shared__ float mg_s[4 * WMAXK];
+  __shared__ int mg_i[4 * WMAXK];
+  const int K = 2 * NB;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  float* bx = buf_x + w * WCAP;
+  int* bi = buf_i + w * WCAP;
+  int cnt = 0;                                           // wave-uniform: cells of bx / bi in use
+  const bool vec = (V & 3) == 0;                         // rows are then 16-B aligned: 4 logits per load
+  constexpr float L2E = 1.4426950408889634f;
+  for (int beam = 0; beam < NBL; ++beam) {
+    const float* row = logits + ((size_t)b * NBL + beam) * V;
+    if (RP) {
+      __syncthreads();                                   // (the previous row's readers are done)
+      if (tid < hist_len) hs_tok[tid] = hist[((size_t)b * NB + beam) * ld_hist + tid];
+      hs_bits[tid] = 0u;
+      __syncthreads();
+      if (tid < hist_len) {
+        const int t = hs_tok[tid];
+        if (t >= 0 && t < V) atomicOr(&hs_bits[(t >> 5) & 255], 1u << (t & 31));
+      }
+      __syncthreads();
+    }
+    // (64 of 8,192 bits are set at most: 127 of 128 candidates skip the walk over the list)
+    auto in_hist = [&](int t) {
+      bool f = false;
+      if ((hs_bits[(t >> 5) & 255] >> (t & 31)) & 1u)
+        for (int h = 0; h < hist_len; ++h) f |= hs_tok[h] == t;
+      return f;
+    };
+    const int ic = cnt;                                  // cells [0, ic): the image so far, (score, flat index); ic <= WKEEP
+    float m = -INFINITY, sum = 0.f;
+    float thr = -INFINITY;                               // wave-uniform bound of the margin form
+    bool strict = false;                                 // wave-uniform: the strict form is on for the rest of the row
+    Cand kth{-INFINITY, 0x7fffffff};                     // strict form: the row's K-th best (logit, index) so far
+    auto wanted = [&](float x, int i) { return strict ? better(x, i, kth.s, kth.i) : x >= thr; };
+    auto reduce = [&]() {                                // over the row's cells [ic, cnt); cnt - ic <= WCAP
+      wave_lds_sync();
+      float ev[WPL];
+      int ei[WPL];
+#pragma unroll
+      for (int j = 0; j < WPL; ++j) {
+        const int p = ic + j * 64 + lane;
+        ev[j] = p < cnt ? bx[p] : -INFINITY;
+        ei[j] = p < cnt ? bi[p] : 0x7fffffff;
+      }
+      wave_lds_sync();                                   // every cell is in a register before any is overwritten
+      if (!strict) {
+        float lm = ev[0];
+#pragma unroll
+        for (int j = 1; j < WPL; ++j) lm = fmaxf(lm, ev[j]);
+        const float t = lanes_kth_largest(lm, K);
+        const float bound = t - 1e-5f * (fabsf(t) + 64.f);
+        if (bound > thr) thr = bound;                    // (t = -inf: the bound stays)
+        int n = ic;
+#pragma unroll
+        for (int j = 0; j < WPL; ++j) {
+          const bool keep = ei[j] != 0x7fffffff && ev[j] >= thr;
+          const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
+          if (keep) {                                    // (n + lanes below <= ic + j * 64 + lane: never past the cell it came from)
+            const int p = n + lanes_below(bal);
+            bx[p] = ev[j]; bi[p] = ei[j];
+          }
+          n += __builtin_popcountll(bal);
+        }
+        cnt = n;
+        if (cnt - ic <= WCAP / 2) { wave_lds_sync(); return; }
+        strict = true;
+      }
+      const Cand c = select_k<WPL>(ev, ei, K);
+      const bool have = c.i != 0x7fffffff;                 // lanes 0 .. min(K, cells) - 1
+      if (have) { bx[ic + lane] = c.s; bi[ic + lane] = c.i; }
+      cnt = ic + __builtin_popcountll(__builtin_amdgcn_ballot_w64(have));
+      kth.s = __shfl(c.s, K - 1, 64);
+      kth.i = __shfl(c.i, K - 1, 64);                    // (fewer than K cells: the empty cell, which everything beats)
+      wave_lds_sync();
+    };
+    auto append = [&](float x, int i, bool ok) {         // needs cnt <= WCAP - 64
+      const unsigned long long bal = __builtin_amdgcn_ballot_w64(ok);
+      if (ok) {
+        const int p = cnt + lanes_below(bal);            // < WCAP by the line above; the test costs nothing
+        if (p < WCAP) { bx[p] = x; bi[p] = i; }
+      }
+      cnt += __builtin_popcountll(bal);
+    };
+    auto push = [&](float x, int i, bool ok) {
+      if (__builtin_amdgcn_ballot_w64(ok) == 0) return;
+      append(x, i, ok);
+      if (cnt > WCAP - 64) reduce();                     // leaves cnt <= WKEEP + WCAP / 2
+    };
+    if (vec) {
+      for (int i0 = 0; i0 < V; i0 += 1024) {
+        const int i = i0 + tid * 4;
+        const bool in = i < V;
+        f32x4 x = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        float mx = -INFINITY;
+        if (in) {
+          x = *(const f32x4*)(row + i);
+          mx = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
+          if (mx > m) {                                   // (m = -inf at first: sum = 0 * 2^-inf = 0)
+            sum *= __builtin_amdgcn_exp2f((m - mx) * L2E);
+            m = mx;
+          }
+          const float ml = m * L2E;
+          sum += (__builtin_amdgcn_exp2f(__builtin_fmaf(x[0], L2E, -ml)) + __builtin_amdgcn_exp2f(__builtin_fmaf(x[1], L2E, -ml))) +
+                 (__builtin_amdgcn_exp2f(__builtin_fmaf(x[2], L2E, -ml)) + __builtin_amdgcn_exp2f(__builtin_fmaf(x[3], L2E, -ml)));
+        }
+        if (__builtin_amdgcn_ballot_w64(in && (strict || mx >= thr)) != 0) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            bool ok = in && i + e != ban && wanted(x[e], i + e);   // (the banned token counts in the softmax, never as a candidate)
+            if (RP && ok) ok = !in_hist(i + e);
+            push(x[e], i + e, ok);
+          }
+        }
+      }
+    } else {
+      for (int i0 = 0; i0 < V; i0 += 256) {
+        const int i = i0 + tid;
+        const bool in = i < V;
+        float x = -INFINITY;
+        if (in) {
+          x = row[i];
+          if (x > m) {
+            sum *= __builtin_amdgcn_exp2f((m - x) * L2E);
+            m = x;
+          }
+          sum += __builtin_amdgcn_exp2f((x - m) * L2E);
+        }
+        bool ok = in && i != ban && wanted(x, i);
+        if (RP && ok) ok = !in_hist(i);
+        push(x, i, ok);
+      }
+    }
+    const float M = block_reduce_max(m, red);
+    // (a thread that saw no element has m = -inf, sum = 0: contributes 0)
+    sum = block_reduce_sum(m == -INFINITY ? 0.f : sum * __builtin_amdgcn_exp2f((m - M) * L2E), red);
+    const float lse = logf(sum);
+    const float bs = beam_scores[b * NB + beam];
+    wave_lds_sync();
+#pragma unroll
+    for (int j = 0; j < WPL; ++j) {                      // the row's cells become candidates of the image, in place
+      const int p = ic + j * 64 + lane;
+      if (p < cnt) { bx[p] = (bx[p] - M) - lse + bs; bi[p] += beam * V; }
+    }
+    if (RP) {                                            // (cnt <= WCAP - 64 after every push)
+      float hs = 0.f;
+      int hi = 0;
+      bool first = false;
+      if (tid < hist_len) {
+        const int t = hs_tok[tid];
+        first = t >= 0 && t < V && t != ban;             // (scatter_ of equal values: a repeated token is penalised once)
+        for (int h = 0; h < tid; ++h) first &= hs_tok[h] != t;
+        if (first) {
+          const float lp = (row[t] - M) - lse;
+          hs = (lp < 0.f ? lp * penalty : lp / penalty) + bs;
+          hi = beam * V + t;
+        }
+      }
+      append(hs, hi, first && hs == hs);                 // (a NaN never enters the buffer)
+    }
+    wave_lds_sync();
+    if (cnt > WKEEP && beam + 1 < NBL) {                 // prune the image's cells [0, cnt) by their final keys
+      float ev[WPL];
+      int ei[WPL];
+#pragma unroll
+      for (int j = 0; j < WPL; ++j) {
+        const int p = j * 64 + lane;
+        ev[j] = p < cnt ? bx[p] : -INFINITY;
+        ei[j] = p < cnt ? bi[p] : 0x7fffffff;
+      }
+      wave_lds_sync();
+      float lm = ev[0];
+#pragma unroll
+      for (int j = 1; j < WPL; ++j) lm = fmaxf(lm, ev[j]);
+      const float t = lanes_kth_largest(lm, K);          // K distinct cells score t or more
+      int n = 0;
+#pragma unroll
+      for (int j = 0; j < WPL; ++j) {
+        const bool keep = ei[j] != 0x7fffffff && ev[j] >= t;
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
+        if (keep) {
+          const int p = n + lanes_below(bal);
+          bx[p] = ev[j]; bi[p] = ei[j];
+        }
+        n += __builtin_popcountll(bal);
+      }
+      cnt = n;
+      if (cnt > WKEEP) {                                 // (wave-uniform) exact: the best K by (score, flat index)
+        const Cand c = select_k<WPL>(ev, ei, K);
+        const bool have = c.i != 0x7fffffff;
+        if (have) { bx[lane] = c.s; bi[lane] = c.i; }
+        cnt = __builtin_popcountll(__builtin_amdgcn_ballot_w64(have));
+      }
+      wave_lds_sync();
+    }
+  }
+  {
+    float cs[WPL];
+    int ci[WPL];
+#pragma unroll
+    for (int j = 0; j < WPL; ++j) {
+      const int p = j * 64 + lane;
+      cs[j] = p < cnt ? bx[p] : -INFINITY;
+      ci[j] = p < cnt ? bi[p] : 0x7fffffff;
+    }
+    const Cand best = select_k<WPL>(cs, ci, K);          // lane r: the r-th best candidate of the image in this wave
+    if (lane < WMAXK) { mg_s[w * WMAXK + lane] = best.s; mg_i[w * WMAXK + lane] = best.i; }
+  }
+  __syncthreads();
+  if (w == 0) {
+    float fs[2] = {mg_s[lane], mg_s[64 + lane]};
+    int fi[2] = {mg_i[lane], mg_i[64 + lane]};
+    const Cand g = select_k<2>(fs, fi, K);
+    if (lane < K) { out_s[(size_t)b * K + lane] = g.s; out_i[(size_t)b * K + lane] = g.i; }
+  }
+}
+
 // ---- teacher-forced form (vidil_logsoftmax_topk_penalty with num_beams == 0): no search, score the GIVEN token of every row
 // (reference: models/med.py:909-917, CrossEntropyLoss(label_smoothing) on the shifted prediction scores).  One workgroup per
 // row, ONE read of the row: every thread keeps an online-softmax state (running maximum m, sum of exp(x - m)), the plain sum
@@ -408,6 +719,57 @@ __global__ void beam_update_kernel(const vidil_beam_state st, const float* __res
   if (st.done[b] && st.n_done != nullptr) atomicAdd(st.n_done, 1);
 }
 
+// nb 5..16: one wave per image.  Lane 0 keeps the books exactly as the thread of beam_update_kernel does (same statements, the
+// chosen beams in LDS instead of dynamically indexed registers); the 64 lanes then copy the nb x cur_len tokens, which is
+// where a single thread spends its time at 16 beams (16 x up to 63 dependent-address loads and stores, one row at a time).
+__global__ __launch_bounds__(64) void beam_update_wide_kernel(const vidil_beam_state st, const float* __restrict__ cand_s,
+                                                              const int32_t* __restrict__ cand_i, int B, int nb, int V,
+                                                              int cur_len, int max_len, int eos_id, int pad_id) {
+  __shared__ float ns[MAXNB_WIDE];
+  __shared__ int nt[MAXNB_WIDE], nsrc[MAXNB_WIDE];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (lane == 0) {
+    const int K = 2 * nb;
+    if (st.done[b]) {
+      for (int j = 0; j < nb; ++j) { ns[j] = 0.f; nt[j] = pad_id; nsrc[j] = b * nb + j; }
+    } else {
+      int slot = 0;
+      for (int rank = 0; rank < K && slot < nb; ++rank) {
+        const int flat = cand_i[b * K + rank];
+        const float sc = cand_s[b * K + rank];
+        const int beam = flat / V, tok = flat - beam * V;
+        if (flat < 0 || beam >= nb) continue;            // (an empty place of the selection, NaN logits: names no row)
+        const int src = b * nb + beam;
+        if (tok == eos_id) {
+          if (rank >= nb) continue;
+          hyp_add(st, b, nb, max_len, st.seqs + (size_t)src * max_len, cur_len, (double)sc);
+        } else {
+          ns[slot] = sc; nt[slot] = tok; nsrc[slot] = src; ++slot;
+        }
+      }
+      for (; slot < nb; ++slot) { ns[slot] = -1e9f; nt[slot] = pad_id; nsrc[slot] = b * nb; }  // (only after empty places)
+      if (st.n_hyp[b] >= nb) {
+        const double cur_score = (double)cand_s[b * K] / (double)cur_len;
+        if (st.worst[b] >= cur_score) st.done[b] = 1;
+      }
+    }
+    if (st.done[b] && st.n_done != nullptr) atomicAdd(st.n_done, 1);
+  }
+  __syncthreads();
+  for (int j = 0; j < nb; ++j) {
+    const int row = b * nb + j;
+    const int32_t* src = st.seqs + (size_t)nsrc[j] * max_len;
+    int32_t* dst = st.seqs_next + (size_t)row * max_len;
+    for (int t = lane; t < cur_len; t += 64) dst[t] = src[t];
+    if (lane == 0) {
+      st.beam_scores[row] = ns[j];
+      st.beam_idx[row] = nsrc[j];
+      st.next_tok[row] = nt[j];
+      dst[cur_len] = nt[j];
+    }
+  }
+}
+
 __global__ void beam_finalize_kernel(const vidil_beam_state st, int B, int nb, int cur_len, int max_len, int eos_id,
                                      int pad_id, int32_t* __restrict__ out_tok, int32_t* __restrict__ out_len,
                                      float* __restrict__ out_score) {
@@ -443,6 +805,31 @@ static int launch_lsm_topk(const float* logits, const float* beam_scores, int32_
   VIDIL_REQUIRE(B > 0 && V > 0, "%s: bad shape", who);
   VIDIL_REQUIRE((long)nb * V < 0x7fffffffL, "%s: nb*V overflows int32", who);
   hipStream_t s = (hipStream_t)stream;
+  if (nb > MAXNB && nb <= MAXNB_WIDE) {
+    // (HF's topk over nb * V scores fails there as well; the narrow kernel fills such places with -inf / 0x7fffffff)
+    VIDIL_REQUIRE((long)nbl * V >= 2L * nb, "%s: beams_in_logits=%d rows of V=%d logits hold fewer than 2*num_beams=%d candidates",
+                  who, nbl, V, 2 * nb);
+    // The logits must be device memory: there is no host path (the Python layer refuses CPU tensors the same way), and a
+    // host address handed to 256 threads per image faults the GPU for everyone on it.  One runtime query per launch, no stream
+    // operation (legal inside a stream capture).  It also keeps argument-check tests, which pass small integers as pointers,
+    // from launching: tests/test_caption_scoring_cpu.py pins VIDIL_EUNSUP for such a 5-beam call.
+    {
+      hipPointerAttribute_t at;
+      const hipError_t e = hipPointerGetAttributes(&at, logits);
+      if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged)) {
+        if (e != hipSuccess) (void)hipGetLastError();      // (the query's own error is not a launch error of a later call)
+        vidil_set_error("%s: num_beams=%d: logits %p are not device memory: host memory is not supported (no CPU path)", who, nb,
+                        (const void*)logits);
+        return VIDIL_EUNSUP;
+      }
+    }
+    if (hist) hipLaunchKernelGGL(lsm_topk_wide_kernel<true>, dim3(B), dim3(256), 0, s, logits, beam_scores, nb, nbl, V, ban_token,
+                                 out_scores, out_index, hist, hist_len, ld_hist, penalty);
+    else hipLaunchKernelGGL(lsm_topk_wide_kernel<false>, dim3(B), dim3(256), 0, s, logits, beam_scores, nb, nbl, V, ban_token,
+                            out_scores, out_index, nullptr, 0, 0, 1.f);
+    VIDIL_CHECK_LAUNCH(who);
+    return VIDIL_OK;
+  }
 #define VIDIL_LSM(NB_)                                                                                                          \
   case NB_:                                                                                                                     \
     if (hist) hipLaunchKernelGGL((lsm_topk_kernel<NB_, true>), dim3(B), dim3(256), 0, s, logits, beam_scores, nbl, V, ban_token, \
@@ -453,7 +840,7 @@ static int launch_lsm_topk(const float* logits, const float* beam_scores, int32_
   switch (nb) {
     VIDIL_LSM(1) VIDIL_LSM(2) VIDIL_LSM(3) VIDIL_LSM(4)
     default:
-      vidil_set_error("%s: num_beams=%d not supported (1..4)", who, nb);
+      vidil_set_error("%s: num_beams=%d not supported (1..16)", who, nb);
       return VIDIL_EUNSUP;
   }
 #undef VIDIL_LSM
@@ -511,7 +898,7 @@ static int check_state(const vidil_beam_state* st, int nb, int max_len, const ch
   VIDIL_REQUIRE(st->seqs && st->seqs_next && st->beam_scores && st->beam_idx && st->next_tok && st->done && st->n_hyp &&
                     st->hyp_score && st->hyp_len && st->hyp_tok && st->worst,
                 "%s: null pointer in state", who);
-  VIDIL_REQUIRE(nb >= 1 && nb <= MAXNB, "%s: num_beams=%d not supported (1..4)", who, nb);
+  VIDIL_REQUIRE(nb >= 1 && nb <= MAXNB_WIDE, "%s: num_beams=%d not supported (1..16)", who, nb);
   VIDIL_REQUIRE(max_len >= 2 && max_len <= MAXLEN, "%s: max_len=%d not supported (2..64)", who, max_len);
   return VIDIL_OK;
 }
@@ -528,6 +915,9 @@ extern "C" int vidil_beam_update(const vidil_beam_state* st, const float* cand_s
     hipError_t e = hipMemsetAsync(st->n_done, 0, sizeof(int32_t), s);
     if (e != hipSuccess) { vidil_set_error("beam_update: memset failed: %s", hipGetErrorString(e)); return VIDIL_ELAUNCH; }
   }
+  if (nb > MAXNB) hipLaunchKernelGGL(beam_update_wide_kernel, dim3(B), dim3(64), 0, s, *st, cand_scores, cand_index, B, nb, V,
+                                     cur_len, max_len, eos_id, pad_id);
+  else
   hipLaunchKernelGGL(beam_update_kernel, dim3((B + 63) / 64), dim3(64), 0, s, *st, cand_scores, cand_index, B, nb, V,
                      cur_len, max_len, eos_id, pad_id);
   VIDIL_CHECK_LAUNCH("beam_update");

@@ -18,7 +18,7 @@ from ._lib import (ACT_GELU_ERF, ACT_NONE, ACT_QUICK_GELU, DT_BF16, DT_F16, DT_F
 __all__ = [
     "gemm", "layernorm", "attention", "patchify_f32", "patchify_u8", "set_cls_row",
     "embed_tokens", "gather_rows", "l2_normalize_rows", "logsoftmax_topk", "token_logprobs", "BeamBuffers",
-    "beam_update", "beam_finalize", "scan_topk", "scan_topk_ws_bytes",
+    "beam_update", "beam_finalize", "MAX_BEAMS", "scan_topk", "scan_topk_ws_bytes",
     "ACT_NONE", "ACT_GELU_ERF", "ACT_QUICK_GELU", "VidilHipError",
 ]
 
@@ -455,6 +455,15 @@ def l2_normalize_rows(x):
 
 
 # ------------------------------------------------------------------------ beam search
+MAX_BEAMS = 16   # widest search of csrc/beam.hip (1..4: register-list selection kernel; 5..16: the streaming one)
+
+
+def require_num_beams(num_beams, who):
+    """Refuse a beam count outside 1..MAX_BEAMS by name, before anything is launched."""
+    if isinstance(num_beams, (bool, float)) or not hasattr(num_beams, "__index__") or not 1 <= int(num_beams) <= MAX_BEAMS:
+        raise VidilHipError(f"{who}: num_beams={num_beams!r} not supported (an integer in 1..{MAX_BEAMS})")
+
+
 def logsoftmax_topk(logits, beam_scores, B, nb, ban_token=-1, out_scores=None, out_index=None, beams_in_logits=None,
                     seqs=None, cur_len=0, penalty=1.0):
     """``seqs`` (i32 [B*nb, max_len], the beams' token ids) with ``cur_len`` and ``penalty``: the repetition penalty of

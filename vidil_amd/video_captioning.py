@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import torch
 
+from . import kernels as K
 from .blip import BLIP_Decoder
 from .video import frame_tokens, middle_frame, phase_timer
 
@@ -29,6 +30,7 @@ def evaluation(model, batches, config, *, videos_per_block=None, timings=None, d
         raise ValueError(f"unknown video_representation {rep!r} (concat_frame | single_frame)")
     kw = dict(num_beams=config["num_beams"], max_length=config["max_length"], min_length=config["min_length"])
     model._require_plain()
+    K.require_num_beams(kw["num_beams"], "video_captioning.evaluation")     # (1..K.MAX_BEAMS, before the first batch is touched)
     dev = next(model.text_decoder.parameters()).device
     lap = phase_timer(timings)
     result, tokens = [], []
