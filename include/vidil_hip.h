@@ -564,6 +564,30 @@ int vidil_sample_top_k_top_p(const float* logits, int32_t* seqs, int32_t* done,
 /* out_index i32 [NF,ncat,topk] = class index WITHIN the category, ordered by */
 /* (score desc, index asc); out_score f32 same shape.                         */
 /* partial: caller workspace, vidil_scan_topk_ws_bytes() bytes.               */
+/*                                                                            */
+/* topk == 0 is the PAIRED SOFTMAX-STATISTICS form (the soft-target           */
+/* contrastive loss over batch + queue, models/blip_retrieval.py:94-131,      */
+/* without a similarity matrix).  NF must be even: P = NF/2 pairs, row p of   */
+/* img is the VALUE row and row P + p the WEIGHT row of pair p.  txt, D and   */
+/* the segments are as above; rows between segments are never read into a     */
+/* result.  Over the classes j of category c, v_j = img[p]·txt[j] and         */
+/* w_j = img[P+p]·txt[j] are the same exact k-ordered chains (v_j has the     */
+/* bits vidil_scan_scores gives), and                                         */
+/*   out_score f32 [P,ncat,5] = max_j v_j, sum_j exp(v_j - max v), max_j w_j, */
+/*                              sum_j exp(w_j - max w),                       */
+/*                              sum_j exp(w_j - max w) * v_j                  */
+/*   out_index i32 [P,ncat]   = argmax_j v_j within the category, lowest      */
+/*                              index on ties (vidil_scan_topk's topk == 1).  */
+/* Nothing behind those extents is written.  The per-lane online-softmax      */
+/* states are merged in a fixed order (8 per row through LDS, then the chunks */
+/* of 256 classes in chunk order: runs of ceil(n/64) consecutive chunks, then */
+/* the 64 runs in order; no atomics), so a pair's five numbers                */
+/* depend on its two rows and the category's classes alone, not on NF, the    */
+/* pair's position or the rest of the launch.  There is no scale argument:    */
+/* callers pre-divide the query rows by the temperature.  partial must be     */
+/* 16-byte aligned, vidil_scan_topk_ws_bytes(NF, NCpad, 0) bytes.  No ABI     */
+/* bump: topk == 0 was VIDIL_EINVAL for every caller built so far, and no     */
+/* signature or struct changes.                                               */
 /* ------------------------------------------------------------------------ */
 int64_t vidil_scan_topk_ws_bytes(int32_t NF, int32_t NCpad, int32_t topk);
 int vidil_scan_topk(const float* img, const float* txt, int32_t NF, int32_t D,

@@ -17,6 +17,15 @@
 // operands; each lane keeps a sorted top-k for (its frame, its classes) in
 // registers; lists are merged through LDS and one partial list per
 // (chunk, frame) goes to the workspace; a second tiny kernel merges chunks.
+//
+// topk == 0 is the paired softmax-statistics form (the soft-target contrastive
+// loss over batch + queue): the 32 rows of a workgroup are 16 VALUE rows and the
+// 16 WEIGHT rows paired with them, a lane keeps online-softmax state (running
+// maximum, sum of exponentials, and the sum weighted by the partner row's
+// score) where the top-k form keeps its sorted list, and the (max, sum,
+// weighted sum) states are merged in the same fixed order: 8 lists per row
+// through LDS, then the chunks of a category in chunk order (one wave per
+// pair and category: stats_merge_kernel).  No atomics.
 #include "common.h"
 
 namespace {
@@ -165,6 +174,161 @@ __global__ void scan_merge_kernel(const ScanP p, int32_t* __restrict__ out_i, fl
   }
 }
 
+// ---- paired softmax statistics (topk == 0) -----------------------------------------------------------------------------------
+// State of one row over a set of classes: m = best score (the top-k order: score desc, index asc), i = its class,
+// s = sum exp(x - m), t = sum exp(x - m) * y, x the row's own score and y the partner row's score of the same class.
+struct Stat {
+  float m, s, t;
+  int i;
+};
+
+__device__ __forceinline__ float rescale(float m_old, float m_new) { return m_old == -INFINITY ? 0.f : expf(m_old - m_new); }
+
+__device__ __forceinline__ void stat_merge(Stat& a, const Stat& b) {
+  const bool take = better(b.m, b.i, a.m, a.i);
+  const float m = take ? b.m : a.m;
+  const float fa = rescale(a.m, m), fb = rescale(b.m, m);
+  a.s = a.s * fa + b.s * fb;
+  a.t = a.t * fa + b.t * fb;
+  a.m = m;
+  a.i = take ? b.i : a.i;
+}
+
+__global__ __launch_bounds__(256) void stats_kernel(const ScanP p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int D = p.D;
+  const int FROW = D + 4;
+  float* Fs = (float*)smem;  // [32][FROW]: rows 0..15 value rows, 16..31 their weight rows; reused for the merge
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hi = lane >> 5, l31 = lane & 31;
+  const int chunk = blockIdx.x, ptile = blockIdx.y;
+  const int P = p.NF >> 1;
+
+  int cat = 0;
+#pragma unroll
+  for (int c = 1; c < MAXCAT; ++c)
+    if (c < p.ncat && chunk >= p.chunk_prefix[c]) cat = c;
+  const int tile0 = (chunk - p.chunk_prefix[cat]) * CT;
+  const int ntiles_cat = (p.seg_len[cat] + 31) / 32;
+  const int seg_len = p.seg_len[cat];
+  const float* txt = p.txt + (size_t)p.seg_start[cat] * D;
+
+  {
+    const int vec_per_row = D / 4;
+    for (int q = tid; q < 32 * vec_per_row; q += 256) {
+      const int r = q / vec_per_row, c = q - r * vec_per_row;
+      const int pair = ptile * 16 + (r & 15);
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (pair < P) v = *(const f32x4*)(p.img + (size_t)((r >> 4) * P + pair) * D + c * 4);
+      *(f32x4*)(Fs + r * FROW + c * 4) = v;
+    }
+  }
+  __syncthreads();
+
+  Stat st = {-INFINITY, 0.f, 0.f, 0x7fffffff};
+  const float* frow = Fs + l31 * FROW + 4 * hi;
+  for (int tt = wave; tt < CT; tt += 4) {
+    const int tile = tile0 + tt;
+    if (tile >= ntiles_cat) break;
+    const int cls = tile * 32 + l31;
+    const int cls_ld = cls < seg_len ? cls : seg_len - 1;
+    const float* trow = txt + (size_t)cls_ld * D + 4 * hi;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll 4
+    for (int c = 0; c < D / 8; ++c) {
+      const f32x4 a = *(const f32x4*)(trow + c * 8);
+      const f32x4 b = *(const f32x4*)(frow + c * 8);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc, 0, 0, 0);
+    }
+    // acc[r]: class = tile*32 + (r&3) + 8*(r>>2) + 4*hi ; row = lane&31 ; the partner row's score sits in lane ^ 16
+    const float m_old = st.m;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c2 = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      if (c2 < seg_len && better(acc[r], c2, st.m, st.i)) { st.m = acc[r]; st.i = c2; }
+    }
+    const float alpha = rescale(m_old, st.m);
+    float s = st.s * alpha, t = st.t * alpha;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c2 = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      const float y = __shfl_xor(acc[r], 16);
+      if (c2 < seg_len) {
+        const float e = expf(acc[r] - st.m);
+        s += e;
+        t = fmaf(e, y, t);
+      }
+    }
+    st.s = s; st.t = t;
+  }
+
+  // ---- merge the 8 states (4 waves x 2 halves) of each row, slot order -------------------------------------------------
+  __syncthreads();  // everyone is done reading Fs
+  f32x4* ms = (f32x4*)smem;  // [8][32] of (m, s, t, bits of i)
+  {
+    const f32x4 v = {st.m, st.s, st.t, __int_as_float(st.i)};
+    ms[(wave * 2 + hi) * 32 + l31] = v;
+  }
+  __syncthreads();
+  if (tid < 32) {
+    Stat a = {-INFINITY, 0.f, 0.f, 0x7fffffff};
+    for (int slot = 0; slot < 8; ++slot) {
+      const f32x4 v = ms[slot * 32 + tid];
+      const Stat b = {v[0], v[1], v[2], __float_as_int(v[3])};
+      stat_merge(a, b);
+    }
+    const f32x4 v = {a.m, a.s, a.t, __int_as_float(a.i)};
+    ((f32x4*)p.part_s)[(size_t)chunk * p.NFpad + ptile * 32 + tid] = v;
+  }
+}
+
+// One wave per (pair, category).  Lane l merges the l-th run of ceil(n / 64) consecutive chunks of the category's n in chunk
+// order; lanes 0 and 1 then merge the 64 run states of the value and of the weight row in lane order.  That is the chunk order
+// in a fixed bracketing which depends on n alone (with n <= 64: plainly one chunk after the other); a thread walking all the
+// chunks of the 57,600-entry queue by itself waits for 226 dependent loads.
+__global__ __launch_bounds__(64) void stats_merge_kernel(const ScanP p, int32_t* __restrict__ out_i, float* __restrict__ out_s) {
+  __shared__ f32x4 runs[2][64];
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const int pair = g / p.ncat, cat = g - pair * p.ncat;
+  const size_t row = (size_t)(pair >> 4) * 32 + (pair & 15);  // the value row; its weight row is 16 further
+  const int c0 = p.chunk_prefix[cat], c1 = p.chunk_prefix[cat + 1];
+  const int per = (c1 - c0 + 63) / 64;
+  const int first = c0 + lane * per, last = first + per < c1 ? first + per : c1;
+  Stat v = {-INFINITY, 0.f, 0.f, 0x7fffffff}, w = v;
+  for (int chunk = first; chunk < last; ++chunk) {
+    const f32x4* part = (const f32x4*)p.part_s + (size_t)chunk * p.NFpad + row;
+    const f32x4 a = part[0], b = part[16];
+    const Stat sa = {a[0], a[1], a[2], __float_as_int(a[3])}, sb = {b[0], b[1], b[2], __float_as_int(b[3])};
+    stat_merge(v, sa);
+    stat_merge(w, sb);
+  }
+  runs[0][lane] = f32x4{v.m, v.s, v.t, __int_as_float(v.i)};
+  runs[1][lane] = f32x4{w.m, w.s, w.t, __int_as_float(w.i)};
+  __syncthreads();
+  if (lane < 2) {
+    Stat a = {-INFINITY, 0.f, 0.f, 0x7fffffff};
+    for (int l = 0; l < 64; ++l) {
+      const f32x4 r = runs[lane][l];
+      const Stat b = {r[0], r[1], r[2], __float_as_int(r[3])};
+      stat_merge(a, b);
+    }
+    runs[lane][0] = f32x4{a.m, a.s, a.t, __int_as_float(a.i)};
+  }
+  __syncthreads();
+  if (lane == 0) {
+    const f32x4 a = runs[0][0], b = runs[1][0];
+    float* o = out_s + (size_t)g * 5;
+    o[0] = a[0]; o[1] = a[1]; o[2] = b[0]; o[3] = b[1]; o[4] = b[2];
+    const int i = __float_as_int(a[3]);
+    out_i[g] = i == 0x7fffffff ? -1 : i;
+  }
+}
+
 // Dense variant for the BLIP retrieval backend (--encoder_version blip needs the k_test = 128 best texts per frame,
 // too many for per-lane register lists): the same exact-f32 score of every (frame, text row), written out.
 __global__ __launch_bounds__(256) void scores_kernel(const float* __restrict__ img, const float* __restrict__ txt, int NF, int D,
@@ -229,10 +393,11 @@ int total_chunks(int ncat, const int32_t* seg_len, int* prefix) {
 }  // namespace
 
 extern "C" int64_t vidil_scan_topk_ws_bytes(int32_t NF, int32_t NCpad, int32_t topk) {
-  if (NF <= 0 || NCpad <= 0 || topk <= 0) return 0;
+  if (NF <= 0 || NCpad <= 0 || topk < 0) return 0;
   // upper bound on chunks: one per CT*32 classes plus one ragged chunk per category
   const int64_t chunks = (int64_t)NCpad / (CT * 32) + MAXCAT + 1;
   const int64_t nfpad = ((int64_t)NF + 31) / 32 * 32;
+  if (topk == 0) return chunks * nfpad * 16;  // one (m, s, t, i) state per (chunk, row)
   return chunks * nfpad * topk * 8;
 }
 
@@ -242,7 +407,9 @@ extern "C" int vidil_scan_topk(const float* img, const float* txt, int32_t NF, i
   VIDIL_REQUIRE(img && txt && seg_start_host && seg_len_host && partial && out_index && out_score, "scan_topk: null pointer");
   VIDIL_REQUIRE(NF > 0 && D >= 8 && D % 8 == 0 && D <= 1024, "scan_topk: NF=%d D=%d (D%%8==0, D<=1024)", NF, D);
   VIDIL_REQUIRE(ncat >= 1 && ncat <= MAXCAT, "scan_topk: ncat=%d (1..%d)", ncat, MAXCAT);
-  VIDIL_REQUIRE(topk >= 1 && topk <= TOPK_MAX, "scan_topk: topk=%d (1..%d)", topk, TOPK_MAX);
+  VIDIL_REQUIRE(topk >= 0 && topk <= TOPK_MAX, "scan_topk: topk=%d (1..%d)", topk, TOPK_MAX);
+  VIDIL_REQUIRE(topk != 0 || NF % 2 == 0,
+                "scan_topk: topk == 0 (paired softmax statistics) needs an even NF, NF/2 value rows then NF/2 weight rows (NF=%d)", NF);
   ScanP p;
   p.img = img; p.txt = txt; p.NF = NF; p.D = D; p.ncat = ncat; p.topk = topk;
   for (int c = 0; c < MAXCAT; ++c) { p.seg_start[c] = 0; p.seg_len[c] = 0; }
@@ -260,6 +427,24 @@ extern "C" int vidil_scan_topk(const float* img, const float* txt, int32_t NF, i
   hipStream_t s = (hipStream_t)stream;
   const int ftiles = p.NFpad / 32;
   VIDIL_REQUIRE(ftiles <= 65535, "scan_topk: too many frames in one call (%d)", NF);
+  if (topk == 0) {  // NF = 2P rows in tiles of 16 + 16: ceil(P / 16) == NFpad / 32 tiles
+    VIDIL_REQUIRE((uintptr_t)partial % 16 == 0, "scan_topk: topk == 0 needs a 16-byte aligned workspace");
+    int smem = 32 * (D + 4) * 4;
+    if (smem < 8 * 32 * 16) smem = 8 * 32 * 16;
+    static int stats_attr_smem = 0;
+    if (smem > stats_attr_smem) {
+      if (hipFuncSetAttribute((const void*)stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
+        vidil_set_error("scan_topk: hipFuncSetAttribute failed");
+        return VIDIL_ELAUNCH;
+      }
+      stats_attr_smem = smem;
+    }
+    hipLaunchKernelGGL(stats_kernel, dim3(nchunks, ftiles), dim3(256), smem, s, p);
+    VIDIL_CHECK_LAUNCH("scan_topk/stats");
+    hipLaunchKernelGGL(stats_merge_kernel, dim3(NF / 2 * ncat), dim3(64), 0, s, p, out_index, out_score);
+    VIDIL_CHECK_LAUNCH("scan_topk/stats-merge");
+    return VIDIL_OK;
+  }
   const int merge_bytes = 8 * 32 * TOPK_MAX * 8;
   int smem = 32 * (D + 4) * 4;
   if (smem < merge_bytes) smem = merge_bytes;

@@ -18,7 +18,7 @@ from ._lib import (ACT_GELU_ERF, ACT_NONE, ACT_QUICK_GELU, DT_BF16, DT_F16, DT_F
 __all__ = [
     "gemm", "layernorm", "attention", "patchify_f32", "patchify_u8", "set_cls_row",
     "embed_tokens", "gather_rows", "l2_normalize_rows", "logsoftmax_topk", "token_logprobs", "BeamBuffers",
-    "beam_update", "beam_finalize", "MAX_BEAMS", "scan_topk", "scan_topk_ws_bytes",
+    "beam_update", "beam_finalize", "MAX_BEAMS", "scan_topk", "scan_topk_ws_bytes", "scan_softmax_stats",
     "ACT_NONE", "ACT_GELU_ERF", "ACT_QUICK_GELU", "VidilHipError",
 ]
 
@@ -677,3 +677,35 @@ def scan_topk(img, txt, seg_start, seg_len, topk, workspace=None):
                                       ncat, ss, sl, topk, _ptr(workspace), _ptr(out_i), _ptr(out_s), _stream()),
           "scan_topk")
     return out_i, out_s
+
+
+def scan_softmax_stats(values, weights, keys, seg_start, seg_len, workspace=None):
+    """The paired softmax-statistics form of the scan (vidil_scan_topk with topk == 0).  values / weights f32 [P,D] (already
+    divided by the temperature); keys f32 [NCpad,D]; seg_start/seg_len: python lists per category.  With v = values[p]·keys[j]
+    and w = weights[p]·keys[j] over the classes j of a category -> (stats f32 [P,ncat,5] = max v, sum exp(v - max v), max w,
+    sum exp(w - max w), sum exp(w - max w)·v;  argmax v i32 [P,ncat]).  No [P,NC] matrix is written."""
+    if values.dim() != 2 or values.shape != weights.shape:
+        raise VidilHipError(f"scan_softmax_stats: values and weights must both be [P,D], got {tuple(values.shape)} and "
+                            f"{tuple(weights.shape)}")
+    if keys.dim() != 2 or keys.shape[1] != values.shape[1]:
+        raise VidilHipError(f"scan_softmax_stats: keys must be [NCpad,{values.shape[1]}], got {tuple(keys.shape)}")
+    if len(seg_start) != len(seg_len):
+        raise VidilHipError(f"scan_softmax_stats: {len(seg_start)} segment starts for {len(seg_len)} lengths")
+    for c, (s0, n) in enumerate(zip(seg_start, seg_len)):
+        if s0 < 0 or n <= 0 or s0 + n > keys.shape[0]:
+            raise VidilHipError(f"scan_softmax_stats: category {c}: rows {s0}..{s0 + n} outside the {keys.shape[0]} key rows")
+    P, D = values.shape
+    ncat = len(seg_start)
+    dev = values.device
+    rows = torch.cat([values, weights], 0)              # _ptr below refuses host tensors and other dtypes
+    need = scan_topk_ws_bytes(2 * P, keys.shape[0], 0)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    out_i = torch.empty((P, ncat), dtype=torch.int32, device=dev)
+    out_s = torch.empty((P, ncat, 5), dtype=torch.float32, device=dev)
+    ss = (C.c_int32 * ncat)(*seg_start)
+    sl = (C.c_int32 * ncat)(*seg_len)
+    check(_lib.load().vidil_scan_topk(_ptr(rows, torch.float32, "scan_softmax_stats.rows"),
+                                      _ptr(keys, torch.float32, "scan_softmax_stats.keys"), 2 * P, D, ncat, ss, sl, 0,
+                                      _ptr(workspace), _ptr(out_i), _ptr(out_s), _stream()), "scan_softmax_stats")
+    return out_s, out_i
