@@ -5,7 +5,7 @@ Run on a GPU, at the commit whose launch sequence is to be kept:
     python tests/golden/make_text_stack_launches.py
 
 tests/test_text_stack_launches_gpu.py runs the same cases through the same recorder and asserts equal traces, so a change of
-the host code (vidil_amd/med.py, blip.py, sentence.py) that is meant to leave the device work alone can show that it did: equal
+the host code (vidil_amd/med.py, decoding.py, blip.py, sentence.py) that is meant to leave the device work alone can show that it did: equal
 traces are the same kernels on the same operands with the same aliasing, hence the same bits.
 
 The recorder wraps every public function of ``vidil_amd.kernels`` (it still calls through) and notes, per call made from outside
@@ -23,6 +23,7 @@ import json
 import lzma
 import os
 import sys
+import types
 
 import torch
 
@@ -301,6 +302,38 @@ def sentence_case(kind):
     return run
 
 
+def search_owner(m, prompt):
+    """A BLIP_Decoder that is nothing but what the beam search asks of its owner: text_decoder, the tokenizer's [SEP] / [PAD]
+    ids and prompt_ids (no ViT, no real tokenizer)."""
+    from vidil_amd.blip import BLIP_Decoder
+
+    class Owner(BLIP_Decoder):
+        def prompt_ids(self, B, device):
+            return torch.tensor([prompt] * B, dtype=torch.int32, device=device)
+
+    owner = Owner.__new__(Owner)
+    torch.nn.Module.__init__(owner)
+    owner.text_decoder = m.dec
+    owner.tokenizer = types.SimpleNamespace(sep_token_id=2, pad_token_id=0)
+    return owner
+
+
+def search_case(calls=1, graphs=None, B=2, P=4, num_beams=3, **kw):
+    """Whole beam searches through generate_ids, B images of 26 encoder rows: ``calls`` consecutive ones on one owner (the first
+    runs plain launches, the second captures its steps — recorded while they are captured —, the third replays: prompt pass
+    and beam_finalize only).  check_done_every=0: without the done-poll, the only branch that depends on timing and the only
+    way into compaction, a search's calls depend neither on values nor on timing."""
+    def run(m, recording):
+        owner = search_owner(m, [5, 6, 7, 8][:P])
+        enc16 = [images(B, 26) for _ in range(calls)]
+        with env(VIDIL_DECODE_GRAPHS=graphs, VIDIL_DECODE_FUSE_LN=None), recording():
+            for e in enc16:
+                owner.generate_ids(e, B, num_beams=num_beams, max_length=8, min_length=3, check_done_every=0, **kw)
+        if calls > 1 and not all(st["graphs_ok"] and st["graphs"] for st in owner._decode_state.values()):
+            raise RuntimeError("the decode steps were not captured: this trace is not the capture / replay schedule")
+    return run
+
+
 def cases():
     c = {}
     for fuse in (None, "0"):
@@ -332,6 +365,11 @@ def cases():
         c[f"parity[{kind},session,tiled=True,5_images_in_blocks_of_2]"] = session_case(True, None, B=5, block=2, kind=kind)
         c[f"parity[{kind},score]"] = score_case("index", kind=kind)
         c[f"parity[{kind},sentence]"] = sentence_case(kind)
+    c["search[eager]"] = search_case(graphs="0")
+    c["search[eager,capture,replay]"] = search_case(calls=3)
+    c["search[one_token_prompt]"] = search_case(P=1)                       # (the VQA form: the arena_prompt route)
+    c["search[6_beams,penalty]"] = search_case(num_beams=6, repetition_penalty=1.2)   # (the wide selection kernel, seqs= / penalty=)
+    c["search[streams=2]"] = search_case(B=4, streams=2)                   # (two parts of 2 images, stepped round robin)
     return c
 
 

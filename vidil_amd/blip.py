@@ -3,9 +3,8 @@
 ``BLIP_Decoder.generate(image, sample=False, num_beams=3, max_length=…, min_length=…)
 -> list[str]``, ``init_tokenizer``, ``create_vit``, ``load_checkpoint``.
 
-The whole beam search (log-softmax, EOS ban, top-2k, BeamSearchScorer bookkeeping,
-KV-cache reorder) runs on the device; the host only enqueues kernels and reads the
-final token ids back once per batch.
+The beam search behind ``generate`` (``generate_ids``) and the decoding session are
+decoding.py's: ``BeamSearchMixin``, ``DecoderSession``.
 """
 from __future__ import annotations
 
@@ -17,7 +16,8 @@ import torch.nn as nn
 
 from . import kernels as K
 from . import video as V
-from .med import BeamArena, BertConfig, BertLMHeadModel, BertModel, CrossKV
+from .decoding import BeamSearchMixin, DecoderSession, DecodeTrace  # noqa: F401  (their home is decoding.py; imported from here too)
+from .med import BertConfig, BertLMHeadModel, BertModel
 from .packing import require_cuda
 from .tokenizer import init_tokenizer, refuse_synthetic_with_checkpoint  # noqa: F401  (init_tokenizer re-exported, reference API)
 from .video import CLIP_MEAN, CLIP_STD, MAX_VIDEO_TOKENS  # noqa: F401  (their home is video.py; imported from here too)
@@ -75,118 +75,6 @@ def load_checkpoint(model, url_or_filename):
     return model, msg
 
 
-class DecodeTrace:
-    """Optional capture of per-step tensors for parity tests (off on the hot path)."""
-
-    def __init__(self):
-        self.logits = []       # f32 [R,V] per forward
-        self.cand_scores = []
-        self.cand_index = []
-        self.scores = None     # f32 [B]: the winning hypothesis' score (sum of log-probabilities / length) as the search reports it
-
-
-class DecoderSession:
-    """Device-resident decoding state of R = B*nb sequences over B images: per-image cross K/V (projected
-    once), the append-only self-attention KV arena + ancestry table, and the two forward entry points the beam
-    loop needs."""
-
-    def __init__(self, text_decoder, enc16, B, nb, max_length, tiled_cross=False):
-        """tiled_cross: keep the image K/V in fragment tiles (BertModel.project_cross_kv(tiled=True)) — every decode
-        step streams them from HBM once, in whole KiB per wave load; the caller guarantees that no launch has more
-        than 32 query rows per image (nb beams x 1 token, or the prompt's tokens)."""
-        self.dec, self.bert = text_decoder, text_decoder.bert
-        cfg = text_decoder.config
-        dev = enc16.device
-        self.B, self.nb, self.R = B, nb, B * nb
-        self.H, self.L = cfg.num_attention_heads, cfg.num_hidden_layers
-        Te = enc16.shape[0] // B
-        self.tiled_cross = tiled_cross
-        self.cross = self.bert.project_cross_kv(enc16, B, Te, tiled=tiled_cross)
-        self.Tcap = max_length
-        # (parity precision mode with vidil_attention_f32: the self-attention K / V cache is f32 too)
-        from .packing import parity_attention_f32
-        arena_dtype = torch.float32 if (self.bert.parity and parity_attention_f32(self.bert)) else enc16.dtype
-        self.arena = BeamArena(self.L, self.Tcap, self.R, cfg.hidden_size, dev, dtype=arena_dtype)
-        self.ws_prefill, self.ws_step = {}, {}
-        self.logits = None
-        # round 6: the decoder's post-LN stack without LayerNorm launches (BertModel._run_layers_fused: raw sums + row partials
-        # between the GEMMs, the LayerNorms folded into the consuming / residual GEMMs) — a property of the SESSION, never of its
-        # size: a caption must not depend on how many images share its search ($VIDIL_DECODE_FUSE_LN=0: the unfused launches)
-        self.fused_ln = self.bert.decoder_fused_ln(enc16.dtype)
-
-    @classmethod
-    def like(cls, parent, B):
-        """A session for ``B`` images with the parent's geometry and EMPTY buffers (no projection): ``adopt`` fills it
-        with the state of a subset of the parent's images in the middle of a search."""
-        self = cls.__new__(cls)
-        self.dec, self.bert = parent.dec, parent.bert
-        self.B, self.nb, self.R = B, parent.nb, B * parent.nb
-        self.H, self.L = parent.H, parent.L
-        self.tiled_cross, self.Tcap = parent.tiled_cross, parent.Tcap
-        pc = parent.cross
-        self.cross = CrossKV(torch.empty((pc.k.shape[0], B) + tuple(pc.k.shape[2:]), dtype=pc.k.dtype, device=pc.k.device),
-                             torch.empty((pc.vt.shape[0], B) + tuple(pc.vt.shape[2:]), dtype=pc.vt.dtype, device=pc.vt.device),
-                             B, pc.Te, pc.NP, tiled=pc.tiled, Tk_cap=pc.Tk_cap, f32=pc.f32)
-        pa = parent.arena
-        self.arena = BeamArena(pa.L, pa.Tcap, self.R, pa.k.shape[-1], pa.k.device, dtype=pa.k.dtype)
-        self.ws_prefill, self.ws_step = {}, {}
-        self.logits = None
-        self.fused_ln = parent.fused_ln
-        return self
-
-    def adopt(self, parent, images, n_pos):
-        """Take over the search state of the parent's images ``images`` (int64 [B] on the device; entries may repeat:
-        padding) after ``n_pos`` cached positions: their cross K/V, their rows of the K/V arena and their ancestry
-        rows, with the slot numbers (= beam rows, always rows of the same image) renumbered."""
-        nb = self.nb
-        j = torch.arange(nb, device=images.device)
-        rows = (images[:, None] * nb + j).view(-1)                                        # parent row of each new row
-        shift = ((torch.arange(self.B, device=images.device) - images) * nb).repeat_interleave(nb).to(torch.int32)
-        self.cross.k.copy_(parent.cross.k.index_select(1, images))
-        self.cross.vt.copy_(parent.cross.vt.index_select(1, images))
-        self.arena.k[:, :n_pos].copy_(parent.arena.k[:, :n_pos].index_select(2, rows))
-        self.arena.v[:, :n_pos].copy_(parent.arena.v[:, :n_pos].index_select(2, rows))
-        self.arena._cur = parent.arena._cur                                                # the orientation step graphs expect
-        self.arena.anc[:, :n_pos] = parent.arena.anc.index_select(0, rows)[:, :n_pos] + shift[:, None]
-        return rows, shift
-
-    def rebind(self, enc16):
-        """Start a new search on another batch of the same shape IN THE SAME BUFFERS (cross K/V re-projected in place,
-        arena orientation reset): device addresses stay what the captured decode-step graphs recorded."""
-        Te = enc16.shape[0] // self.B
-        self.cross = self.bert.project_cross_kv(enc16, self.B, Te, out=self.cross, tiled=self.tiled_cross)
-        self.arena._cur = 0
-
-    def prefill(self, ids_i32, P, shared=False):
-        """Prompt pass.  shared=False: ids_i32 int32 [R*P], every row decoded -> logits f32 [R,V] (what HF
-        generate() does).  shared=True: ids_i32 int32 [B*P], ONE row per image -> logits f32 [B,V]: the nb beams of
-        an image are identical until the first beam update (models/blip.py:130-138 repeats the same prompt and
-        image nb times), so their prompt pass is computed once and its K/V are stored once (arena slot b*nb, which
-        the ancestry rows of all nb beams point at)."""
-        rows = self.B if shared else self.R
-        h32, h16 = self.bert.embed(ids_i32, P, 0)
-        # the prompt block attends to itself through one scratch K / V^T pair shared by all layers
-        sk, sv, NPp = self.bert.scratch_kv(rows, P, h16.dtype, ids_i32.device)
-        self.arena.init_prompt(P, self.nb if shared else 1)
-        self.bert.run_layers(h32, h16, rows=rows, T=P, self_k=sk, self_vt=sv, t_off=0, Tk_cap=P, NPs=NPp, causal=True,
-                             kv_len=None, cross=self.cross, cross_group=1 if shared else self.nb, ws=self.ws_prefill,
-                             arena=self.arena, arena_slot_stride=self.nb if shared else 1, fused=self.fused_ln,
-                             arena_prompt=(P == 1 and shared))   # (a shared one-token prompt is still a prompt block: slot b*nb)
-        return self.dec.lm_logits(h16, rows, P, h32=h32)
-
-    def step(self, next_tok_i32, beam_idx_i32, past_len):
-        """Re-point the beams at their new histories (``beam_idx``: models/med.py:951-955 _reorder_cache, here a
-        reorder of the ancestry table only), then one cached forward of the single new token at position
-        ``past_len``.  Returns logits f32 [R,V]."""
-        self.arena.reorder(beam_idx_i32, past_len)
-        h32, h16 = self.bert.embed(next_tok_i32, 1, past_len)
-        self.bert.run_layers(h32, h16, rows=self.R, T=1, self_k=None, self_vt=None, t_off=past_len, Tk_cap=self.Tcap,
-                             NPs=0, causal=False, kv_len=None, cross=self.cross, cross_group=self.nb, ws=self.ws_step,
-                             arena=self.arena, fused=self.fused_ln)
-        self.logits = self.dec.lm_logits(h16, self.R, 1, out=self.logits, h32=h32)
-        return self.logits
-
-
 class BLIP_Base(nn.Module):
     """The reference's feature extractor (models/blip.py:22-74): a ViT and the cross-attending text encoder, no heads."""
 
@@ -233,7 +121,7 @@ def blip_feature_extractor(pretrained="", **kwargs):
     return model
 
 
-class BLIP_Decoder(nn.Module):
+class BLIP_Decoder(BeamSearchMixin, nn.Module):
     def __init__(self, med_config="configs/med_config.json", image_size=384, vit="base", vit_grad_ckpt=False,
                  vit_ckpt_layer=0, prompt="a picture of ", tokenizer=None):
         super().__init__()
@@ -252,263 +140,12 @@ class BLIP_Decoder(nn.Module):
         ids[:, 0] = self.tokenizer.bos_token_id
         return ids[:, :-1].to(torch.int32).to(device)
 
-    # ------------------------------------------------------------------ beam decode
-    @torch.no_grad()
-    def generate_ids(self, enc16, B, *, num_beams=3, max_length=30, min_length=10, trace: DecodeTrace = None,
-                     check_done_every=2, streams=1, compact_min=256, repetition_penalty=1.0):
-        """enc16: f16 [B*Te, width] image tokens of B images.  Returns (tokens i32 [B,max_length], lens i32 [B]):
-        best hypothesis incl. the prompt, then [SEP] if it fits, then [PAD].
-
-        ``streams`` > 1: the images are cut into that many contiguous parts whose searches run side by side on their
-        own HIP streams (``_beam_search`` is a generator that yields after queueing each step; the parts are stepped
-        round robin).  Measured at 3,072 images: 2 parts +0.2 %, 3 parts -1.4 %, 4 parts -3.8 % of the whole step — the
-        ~160 launches of a decode step are short but each already covers the chip (decode time scales ~1/CUs under a
-        CU mask), so the default stays 1; kept for small batches per part of a larger job.
-        A search is per image, so the tokens do not depend on the split.
-
-        ``repetition_penalty`` != 1.0 (models/blip.py:127,161; the captioning call site leaves it at 1.0): the candidate
-        selection of every step penalises the log-probabilities of the tokens a beam already holds, prompt included
-        (``vidil_logsoftmax_topk_penalty``; oracle/beam_ref.py ``repetition_penalty``)."""
-        require_cuda(enc16, "BLIP_Decoder.generate")
-        K.require_num_beams(num_beams, "generate")          # (1..K.MAX_BEAMS; refused here, not in the middle of a search)
-        if not repetition_penalty > 0:
-            raise ValueError(f"repetition_penalty must be a strictly positive float, got {repetition_penalty}")   # (HF's message)
-        kw = dict(num_beams=num_beams, max_length=max_length, min_length=min_length, check_done_every=check_done_every,
-                  compact_min=compact_min, repetition_penalty=float(repetition_penalty))
-        if streams <= 1 or trace is not None or B < 2 * streams:
-            g = self._beam_search(enc16, B, trace=trace, slot=0, **kw)
-            while True:
-                try:
-                    next(g)
-                except StopIteration as done:
-                    return done.value
-        main = torch.cuda.current_stream()
-        side = self.__dict__.setdefault("_decode_streams", {})
-        Te = enc16.shape[0] // B
-        bounds = [(B * i // streams, B * (i + 1) // streams) for i in range(streams)]
-        fork = torch.cuda.Event()
-        fork.record(main)
-        gens = []
-        for i, (lo, hi) in enumerate(bounds):
-            st = side.get((i, enc16.device))
-            if st is None:
-                st = side[(i, enc16.device)] = torch.cuda.Stream(device=enc16.device)
-            st.wait_event(fork)
-            gens.append((st, self._beam_search(enc16[lo * Te:hi * Te], hi - lo, slot=i, **kw)))
-        results = [None] * streams
-        live = list(range(streams))
-        while live:
-            for i in list(live):
-                st, g = gens[i]
-                with torch.cuda.stream(st):
-                    try:
-                        next(g)
-                    except StopIteration as done:
-                        results[i] = done.value
-                        live.remove(i)
-        for i, (st, _) in enumerate(gens):
-            join = torch.cuda.Event()
-            join.record(st)
-            main.wait_event(join)
-            for t in results[i]:
-                t.record_stream(main)
-        return torch.cat([r[0] for r in results]), torch.cat([r[1] for r in results])
-
-    def _beam_search(self, enc16, B, *, num_beams, max_length, min_length, trace=None, check_done_every=2, slot=0,
-                     compact_min=256, repetition_penalty=1.0):
-        """Generator: queues the prompt pass and one decode step per ``next()`` on the current stream, returns
-        (tokens, lens) through StopIteration."""
-        dec, bert = self.text_decoder, self.text_decoder.bert
-        cfg = dec.config
-        tok = self.tokenizer
-        eos, pad = tok.sep_token_id, tok.pad_token_id
-        dev = enc16.device
-        nb = num_beams
-        V = cfg.vocab_size
-        # Session state (KV arena, cross K/V, beam buffers) is kept per shape (and per stream slot) and reused by the
-        # next batch: besides saving the allocations it keeps every device address stable, which is what lets the
-        # decode steps — ~160 launches of 8-30 us kernels each, issued faster by the GPU than Python can enqueue them
-        # — be captured once into HIP graphs (one per step index: the position is baked into the launches) and replayed.
-        prompt = self.prompt_ids(B, dev)
-        P = prompt.shape[1]
-        rp = float(repetition_penalty)             # (part of the session keys: the step graphs bake it into their launches)
-        key = (B, nb, max_length, min_length, str(dev), enc16.shape[0] // B, P, rp, slot)
-        cache = self.__dict__.setdefault("_decode_state", {})
-        st = cache.get(key)
-        packs = (dec.packed(), bert.packed())     # captured graphs hold the addresses of these packed weights
-        if st is not None and not (st["packs"][0] is packs[0] and st["packs"][1] is packs[1]):
-            st = None                              # parameters changed since the capture (e.g. a checkpoint was loaded)
-        if st is None:
-            if len(cache) >= 8:
-                # make room: the compact sessions first (each holds its own cross K/V, arena and step graphs — roughly
-                # +1.6x of a main session's memory over the four bucket sizes — and is cheap to rebuild); if that was not
-                # enough, the LEAST RECENTLY USED main sessions go, one at a time, until there is room — the sessions a
-                # pipeline alternates between keep their captured step graphs when an eighth shape shows up (ADVICE r2:
-                # this used to be cache.clear())
-                for k_ in [k_ for k_ in cache if isinstance(k_[-1], tuple)]:
-                    del cache[k_]
-                while len(cache) >= 8:
-                    del cache[min(cache, key=lambda k_: cache[k_].get("last_used", 0))]
-            # (the shared prompt pass has P query rows per image, a decode step nb)
-            st = cache[key] = dict(sess=DecoderSession(dec, enc16, B, nb, max_length, tiled_cross=P <= 32 and nb <= 32),
-                                   bufs=K.BeamBuffers(B, nb, max_length, dev), graphs={}, pool=None, calls=0, packs=packs,
-                                   graphs_ok=os.environ.get("VIDIL_DECODE_GRAPHS", "1") != "0",
-                                   n_done_host=torch.zeros((1,), dtype=torch.int32, pin_memory=True))
-        else:
-            st["sess"].rebind(enc16)
-        self.__dict__["_decode_clock"] = st["last_used"] = self.__dict__.get("_decode_clock", 0) + 1
-        st["calls"] += 1
-        st["bufs"].reset(prompt)
-        # `cur`: the session the loop is driving — the full batch, or (after compaction, below) a smaller session that
-        # adopted the images that are still searching
-        cur = dict(st=st, sess=st["sess"], bufs=st["bufs"], B=B,
-                   use_graphs=st["graphs_ok"] and trace is None and st["calls"] >= 2)    # the first batch warms every kernel up
-
-        def first_unit(logits):
-            bufs = cur["bufs"]
-            cs, ci = K.logsoftmax_topk(logits, bufs.beam_scores, B, nb, eos if P < min_length else -1, beams_in_logits=1,
-                                       seqs=bufs.seqs if rp != 1.0 else None, cur_len=P, penalty=rp)
-            if trace is not None:
-                trace.logits.append(logits.clone()); trace.cand_scores.append(cs.clone()); trace.cand_index.append(ci.clone())
-            K.beam_update(bufs, cs, ci, V, P, eos, pad)
-
-        def unit(c):
-            """Decode step at length c: forward of the token appended last, candidate selection, beam update."""
-            sess, bufs = cur["sess"], cur["bufs"]
-            logits = sess.step(bufs.next_tok, bufs.beam_idx, c - 1)
-            cs, ci = K.logsoftmax_topk(logits, bufs.beam_scores, cur["B"], nb, eos if c < min_length else -1,
-                                       seqs=bufs.seqs if rp != 1.0 else None, cur_len=c, penalty=rp)
-            if trace is not None:
-                trace.logits.append(logits.clone()); trace.cand_scores.append(cs.clone()); trace.cand_index.append(ci.clone())
-            K.beam_update(bufs, cs, ci, V, c, eos, pad)
-
-        # ---- finished images leave the batch (VIDIL_DECODE_COMPACT=0 switches it off) --------------------------------
-        # Real captions end at different lengths; an image whose nb hypotheses are complete only burns rows.  When the
-        # polled counter says the searching images fit the next smaller bucket (3/4, 1/2, 1/4, 1/8 of B, at least
-        # `compact_min` images), they move to a session of that size: cross K/V, arena rows, ancestry rows and beam
-        # state are gathered (a few ms at 1,500 images), the finished ones are finalised where they are.  A search is
-        # per image and every kernel's arithmetic is independent of the batch around a row, so the tokens do not change.
-        # The random-weight benchmark never triggers this (nothing finishes before the length limit).
-        compact = compact_min > 0 and trace is None and os.environ.get("VIDIL_DECODE_COMPACT", "1") != "0"
-        gran = 64 if compact_min >= 64 else 1                                   # bucket sizes in whole 64-image steps
-        buckets = sorted({max(compact_min, -(-(B * f) // (8 * gran)) * gran) for f in (6, 4, 2, 1)}, reverse=True) if compact else []
-        buckets = [b for b in buckets if b < B]
-        final_tok = final_len = None
-        orig = None                                # device int64: original image of each image of the current session
-
-        def retire_and_compact(cur_len):
-            """Blocking: read the exact done mask, finalise everything into the result buffers, move the searching images
-            into the largest bucket they fit.  Returns False when they do not fit a smaller bucket after all."""
-            nonlocal final_tok, final_len, orig
-            bufs, sess = cur["bufs"], cur["sess"]
-            active = (bufs.done == 0).nonzero().view(-1)                      # (host wait: exact state)
-            A = int(active.numel())
-            fit = [b for b in buckets if A <= b < cur["B"]]
-            if not fit or A == 0:
-                return False
-            Bp = fit[-1]
-            images = torch.cat([active, active[-1:].expand(Bp - A)])           # padding: copies of the last one, marked done
-            key2 = (Bp, nb, max_length, min_length, str(dev), enc16.shape[0] // B, P, rp, ("compact", slot))
-            st2 = cache.get(key2)
-            if st2 is not None and not (st2["packs"][0] is packs[0] and st2["packs"][1] is packs[1]):
-                st2 = None
-            if st2 is None:
-                st2 = cache[key2] = dict(sess=DecoderSession.like(st["sess"], Bp), bufs=K.BeamBuffers(Bp, nb, max_length, dev),
-                                         graphs={}, pool=None, calls=0, packs=packs, graphs_ok=st["graphs_ok"],
-                                         n_done_host=torch.zeros((1,), dtype=torch.int32, pin_memory=True), last_call=-1)
-            if st2.get("last_call") != st["calls"]:                             # one use per search of the parent
-                st2["calls"] += 1
-                st2["last_call"] = st["calls"]
-            rows, shift = st2["sess"].adopt(sess, images, cur_len)
-            nb2 = st2["bufs"]
-            if getattr(nb2, "swapped", False) != getattr(bufs, "swapped", False):
-                nb2.swap()                                                      # same buffer roles as the step graphs saw
-            nb2.seqs.copy_(bufs.seqs.index_select(0, rows))
-            nb2.beam_scores.copy_(bufs.beam_scores.index_select(0, rows))
-            nb2.next_tok.copy_(bufs.next_tok.index_select(0, rows))
-            nb2.beam_idx.copy_(bufs.beam_idx.index_select(0, rows) + shift)
-            for name in ("done", "n_hyp", "hyp_score", "hyp_len", "hyp_tok", "worst"):
-                getattr(nb2, name).copy_(getattr(bufs, name).index_select(0, images))
-            nb2.done[A:] = 1
-            nb2.n_done.fill_(Bp - A)
-            # only now: beam_finalize ADDS the running beams of unfinished images to their hypothesis lists in place
-            # (BeamSearchScorer.finalize does), which must not reach the copies made above; the state left behind in
-            # the old session is dead — its next search starts with reset()
-            out_tok, out_len, _ = K.beam_finalize(bufs, cur_len, eos, pad)
-            if final_tok is None:
-                final_tok, final_len = out_tok, out_len
-                orig = torch.arange(B, device=dev)
-            else:
-                final_tok[orig] = out_tok[:orig.numel()]
-                final_len[orig] = out_len[:orig.numel()]
-            orig = orig.index_select(0, active)
-            cur.update(st=st2, sess=st2["sess"], bufs=nb2, B=Bp,
-                       use_graphs=st2["graphs_ok"] and st2["calls"] >= 2)
-            return True
-
-        # ---- prompt pass, once per image: the beams of an image are identical until the first update
-        first_unit(cur["sess"].prefill(prompt.contiguous().view(-1), P, shared=True))
-        yield
-        cur_len = P + 1
-        probe = None
-        while cur_len < max_length:
-            # "every image has its nb finished hypotheses" (BeamSearchScorer.is_done) is polled WITHOUT a host wait: the
-            # counter travels to pinned memory behind an event and is looked at when it has arrived.  A step queued
-            # after the last image finished changes nothing (finished images are skipped by beam_update, like
-            # process() skips done batches, and beam_finalize takes their stored hypotheses).
-            if check_done_every and trace is None and cur_len % check_done_every == 0:
-                if probe is not None and probe.query():
-                    n_done = int(cur["st"]["n_done_host"][0])
-                    probe = None
-                    if n_done == cur["B"]:
-                        break
-                    if buckets and max_length - cur_len >= 3 and any(cur["B"] - n_done <= b < cur["B"] for b in buckets):
-                        retire_and_compact(cur_len)
-                if probe is None:
-                    cur["st"]["n_done_host"].copy_(cur["bufs"].n_done, non_blocking=True)
-                    probe = torch.cuda.Event()
-                    probe.record()
-            elif check_done_every and trace is not None and int(cur["bufs"].n_done.item()) == B:
-                break                        # parity traces stop exactly where the reference's loop stops
-            g = cur["st"]["graphs"].get(cur_len) if cur["use_graphs"] else None
-            if g is not None:
-                g.replay()
-                cur["sess"].arena._cur ^= 1      # the host-side halves of arena.reorder() and beam_update()
-                cur["bufs"].swap()
-            elif cur["use_graphs"]:
-                try:
-                    g = torch.cuda.CUDAGraph()
-                    # thread_local: other threads (the RCCL watchdog of a multi-GPU run) may touch the runtime meanwhile
-                    with torch.cuda.graph(g, pool=cur["st"]["pool"], capture_error_mode="thread_local"):
-                        unit(cur_len)
-                    cur["st"]["pool"] = g.pool()
-                    cur["st"]["graphs"][cur_len] = g
-                    g.replay()            # capture records, replay executes (host-side state already advanced)
-                except Exception as e:    # capture unsupported here: finish this batch with plain launches, loudly
-                    import warnings
-                    warnings.warn(f"vidil_amd: decode-step graph capture failed ({e!r}); continuing without graphs")
-                    torch.cuda.synchronize()
-                    for s_ in cache.values():
-                        s_["graphs_ok"] = False
-                        s_["graphs"].clear()
-                    inner = self._beam_search(enc16, B, num_beams=num_beams, max_length=max_length, min_length=min_length,
-                                              trace=trace, check_done_every=check_done_every, slot=slot, compact_min=compact_min,
-                                              repetition_penalty=rp)
-                    return (yield from inner)
-            else:
-                unit(cur_len)
-            cur_len += 1
-            yield
-        out_tok, out_len, out_score = K.beam_finalize(cur["bufs"], cur_len, eos, pad)
-        if trace is not None:
-            trace.scores = out_score          # (a traced search never compacts: one score per image)
-        if final_tok is None:
-            return out_tok, out_len
-        final_tok[orig] = out_tok[:orig.numel()]
-        final_len[orig] = out_len[:orig.numel()]
-        return final_tok, final_len
-
     # ------------------------------------------------------------------ nucleus sampling
+    def _fresh_seed(self):
+        """The seed of a sampling call that is given none: torch's initial seed, moved on by every such call of this model."""
+        self._sample_calls = getattr(self, "_sample_calls", 0) + 1
+        return (torch.initial_seed() + (self._sample_calls << 32)) & 0xFFFFFFFFFFFFFFFF
+
     @torch.no_grad()
     def sample_ids(self, enc16, B, *, top_p=0.9, max_length=30, min_length=10, top_k=50, repetition_penalty=1.1,
                    seed=None, row_offset=0, check_done_every=4):
@@ -521,8 +158,7 @@ class BLIP_Decoder(nn.Module):
         eos, pad = tok.sep_token_id, tok.pad_token_id
         dev = enc16.device
         if seed is None:
-            self._sample_calls = getattr(self, "_sample_calls", 0) + 1
-            seed = (torch.initial_seed() + (self._sample_calls << 32)) & 0xFFFFFFFFFFFFFFFF
+            seed = self._fresh_seed()
         prompt = self.prompt_ids(B, dev)
         P = prompt.shape[1]
         sess = DecoderSession(self.text_decoder, enc16, B, 1, max_length, tiled_cross=P <= 32)
@@ -711,8 +347,7 @@ class BLIP_Video_Decoder(BLIP_Decoder):
             K.require_num_beams(num_beams, "BLIP_Video_Decoder.generate")   # (before the ViT runs)
         tok16, B = self._tokens(video)
         if sample and seed is None:
-            self._sample_calls = getattr(self, "_sample_calls", 0) + 1
-            seed = (torch.initial_seed() + (self._sample_calls << 32)) & 0xFFFFFFFFFFFFFFFF
+            seed = self._fresh_seed()
         Te = tok16.shape[0] // B
         per = self.videos_per_block(Te) if videos_per_block is None else int(videos_per_block)
         if per < 1:

@@ -35,7 +35,8 @@ import torch.nn as nn
 
 from . import kernels as K
 from . import video as V
-from .blip import BLIP_Decoder, create_vit, load_checkpoint, resolve_med_config
+from .blip import create_vit, load_checkpoint, resolve_med_config
+from .decoding import BeamSearchMixin
 from .med import BertConfig, BertLMHeadModel, BertModel
 from .packing import FP8, compute_dtype, fp8_companion, require_cuda, set_compute_dtype, set_parity_mode
 from .tokenizer import init_tokenizer, refuse_synthetic_with_checkpoint
@@ -47,7 +48,7 @@ VQA_LABEL_SMOOTHING = 0.1        # models/med.py:916 (the loss `rank_answer` neg
 MAX_IMAGE_TOKENS = 768           # keys the attention kernels serve (vidil_attention: Nk <= 768): ViT-B/16 up to 432 px
 
 
-class BLIP_VQA(nn.Module):
+class BLIP_VQA(BeamSearchMixin, nn.Module):
     #: read by packing.set_parity_mode / set_compute_dtype: why this model refuses the parity precision mode and fp8
     plain_only = "question answering is built for plain f16 / bf16 operands (masked cross-attention has no error-compensated form)"
 
@@ -124,15 +125,10 @@ class BLIP_VQA(nn.Module):
         """models/blip_vqa.py:97: the one-token [DEC] prompt."""
         return torch.full((B, 1), self.tokenizer.bos_token_id, dtype=torch.int32, device=device)
 
-    # the device-resident beam search of the captioner (per-shape DecoderSession cache, captured step graphs): it asks its
-    # owner for text_decoder, tokenizer and prompt_ids only
-    generate_ids = BLIP_Decoder.generate_ids
-    _beam_search = BLIP_Decoder._beam_search
-
     @torch.no_grad()
     def generate_answer_ids(self, states16, Q):
-        """Beam search over the UNMASKED question states [Q*Tq, C] (see the module docstring).  Returns (tokens i32 [Q, 10]:
-        [DEC], the answer, [SEP] if it fits, then [PAD]; lens i32 [Q])."""
+        """The captioner's beam search (BeamSearchMixin.generate_ids) over the UNMASKED question states [Q*Tq, C] (see the
+        module docstring).  Returns (tokens i32 [Q, 10]: [DEC], the answer, [SEP] if it fits, then [PAD]; lens i32 [Q])."""
         self._require_plain()
         return self.generate_ids(states16, Q, num_beams=VQA_NUM_BEAMS, max_length=VQA_MAX_LENGTH, min_length=VQA_MIN_LENGTH)
 

@@ -557,12 +557,13 @@ class BeamBuffers:
         self.hyp_tok = torch.zeros((B, nb, max_len), **i32)
         self.worst = torch.full((B,), 1e9, dtype=torch.float64, device=device)
         self.n_done = torch.zeros((1,), **i32)
+        self.swapped = False
 
     def reset(self, prompt_ids):
         """prompt_ids: int32 [B, P]; beams of an image start identical, scores [0,-1e9,...]."""
         B, nb = self.B, self.nb
         P = prompt_ids.shape[1]
-        if getattr(self, "swapped", False):   # every search starts from the same buffer orientation (captured
+        if self.swapped:                      # every search starts from the same buffer orientation (captured
             self.swap()                        # decode-step graphs bake the pointers of each step in)
         self.seqs.zero_()
         self.seqs[:, :P] = prompt_ids.repeat_interleave(nb, dim=0)
@@ -579,7 +580,7 @@ class BeamBuffers:
 
     def swap(self):
         self.seqs, self.seqs_next = self.seqs_next, self.seqs
-        self.swapped = not getattr(self, "swapped", False)
+        self.swapped = not self.swapped
 
 
 def beam_update(bufs: BeamBuffers, cand_scores, cand_index, V, cur_len, eos_id, pad_id):
