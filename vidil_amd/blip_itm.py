@@ -30,11 +30,16 @@ class BLIP_ITM(PackedCache, nn.Module):
         self.tokenizer = tokenizer if tokenizer is not None else init_tokenizer()
         cfg = BertConfig.from_json_file(resolve_med_config(med_config))
         cfg.encoder_width = vision_width
+        self._adapt_med_config(cfg)
         self.text_encoder = BertModel(config=cfg, add_pooling_layer=False)
         text_width = cfg.hidden_size
         self.vision_proj = nn.Linear(vision_width, embed_dim)   # 'itc' head (forward(match_head='itc'))
         self.text_proj = nn.Linear(text_width, embed_dim)
         self.itm_head = nn.Linear(text_width, 2)
+
+    def _adapt_med_config(self, cfg):
+        """The text encoder's configuration as read from ``med_config``, before the encoder is built from it (``self.tokenizer``
+        is set): nothing here; BLIP_Pretrain resizes the vocabulary to its tokenizer's."""
 
     def _pack(self):
         p = dict(itm_w=w16(self.itm_head.weight, dtype=self.cdt), itm_b=v32(self.itm_head.bias), parity=self.parity)

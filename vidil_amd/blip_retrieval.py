@@ -124,9 +124,13 @@ class BLIP_Retrieval(BLIP_ITM):
             store[QUEUE_HEAD:] = nn.functional.normalize(torch.randn(D, Q), dim=0).t().to(dev)
             self.__dict__["_store_" + name] = store
             self.register_buffer(name, store[QUEUE_HEAD:].t())
+        self._register_queue_pointers(Q, dev)
+        return self
+
+    def _register_queue_pointers(self, Q, dev):
+        """The queues' bookkeeping buffers under the reference class's names (BLIP_Pretrain has ``queue_ptr`` and no ids)."""
         self.register_buffer("idx_queue", torch.full((1, Q), -100, device=dev))
         self.register_buffer("ptr_queue", torch.zeros(1, dtype=torch.long, device=dev))
-        return self
 
     @property
     def model_pairs(self):
@@ -164,14 +168,19 @@ class BLIP_Retrieval(BLIP_ITM):
     @torch.no_grad()
     def _dequeue_and_enqueue(self, image_feat, text_feat, idxs):
         """:268-286 at world size 1: columns ptr .. ptr + B of the queues := the momentum features (rows of the key stores)."""
+        ptr = self._enqueue_features(image_feat, text_feat, self.ptr_queue)
+        self.idx_queue[:, ptr:ptr + image_feat.shape[0]] = idxs.view(1, -1).to(self.idx_queue)
+
+    def _enqueue_features(self, image_feat, text_feat, pointer):
+        """Rows ptr .. ptr + B of both key stores := the features, ``pointer`` (the class's pointer buffer) moves on; -> the old ptr."""
         B = image_feat.shape[0]
         if self.queue_size % B:
             raise ValueError(f"{type(self).__name__}: queue_size={self.queue_size} is not a multiple of the batch size {B}")
-        ptr = int(self.ptr_queue)
+        ptr = int(pointer)
         self._key_store("image_queue")[QUEUE_HEAD + ptr:QUEUE_HEAD + ptr + B] = image_feat
         self._key_store("text_queue")[QUEUE_HEAD + ptr:QUEUE_HEAD + ptr + B] = text_feat
-        self.idx_queue[:, ptr:ptr + B] = idxs.view(1, -1).to(self.idx_queue)
-        self.ptr_queue[0] = (ptr + B) % self.queue_size
+        pointer[0] = (ptr + B) % self.queue_size
+        return ptr
 
     def _pack(self):
         p = super()._pack()
@@ -289,7 +298,8 @@ class BLIP_Retrieval(BLIP_ITM):
             raise ValueError(f"{who}: f32 [B,3,S,S] expected, got {tuple(image.shape)}")
 
     def _itc_direction(self, a, a_m, keys_m, store, alpha, temp):
-        """One direction of the soft-target contrastive loss (:123-139) -> f32 [B] row losses.  a, a_m: the student and the
+        """One direction of the soft-target contrastive loss (:123-139) -> (f32 [B] row losses, f32 [B,B] the student rows
+        against the batch's momentum keys over temp — the block the diagonal is read from).  a, a_m: the student and the
         momentum rows [B, D] (unit norm); keys_m: the other modality's momentum batch features, written to rows [0, B) of its key
         store, whose queue segment starts at QUEUE_HEAD."""
         B = a.shape[0]
@@ -300,20 +310,23 @@ class BLIP_Retrieval(BLIP_ITM):
         ev, ew = torch.exp(st[..., 0] - m), torch.exp(st[..., 2] - mw)
         lse = m[:, 0] + torch.log((st[..., 1] * ev).sum(1))
         soft = (st[..., 4] * ew).sum(1) / (st[..., 3] * ew).sum(1)                              # sum_j softmax(m)_j s_j
-        diag = K.scan_scores(q, store[:B]).diagonal()
-        return lse - alpha * soft - (1.0 - alpha) * diag
+        block = K.scan_scores(q, store[:B])
+        return lse - alpha * soft - (1.0 - alpha) * block.diagonal(), block
 
     def _draw_negatives(self, sim, idx, seed, stream):
         """One negative column per row of sim f32 [B,B] (already / temp): weights = softmax with same-idx entries zeroed
         (:200-209); the draw is the first j with cumsum_j > u * cumsum_last, u = philox_uniform(seed, row, stream)."""
-        B = sim.shape[0]
-        w = torch.softmax(sim, dim=1).masked_fill(idx.view(-1, 1) == idx.view(1, -1), 0.0)
+        return self._draw_from_weights(torch.softmax(sim, dim=1).masked_fill(idx.view(-1, 1) == idx.view(1, -1), 0.0), seed, stream)
+
+    def _draw_from_weights(self, w, seed, stream):
+        """The inverse-CDF draw of the Philox contract, one column per row of the weights w f32 [B,B]."""
+        B = w.shape[0]
         c = torch.cumsum(w, dim=1)
         empty = (c[:, -1] <= 0).nonzero()
         if empty.numel():
             raise ValueError(f"{type(self).__name__}: row {int(empty[0])} has no admissible negative (every weight of its masked "
                              "softmax is zero)")
-        u = philox_uniform(seed, torch.arange(B), stream, sim.device)
+        u = philox_uniform(seed, torch.arange(B), stream, w.device)
         return (c <= (u * c[:, -1])[:, None]).sum(1).clamp_(max=B - 1)
 
     @torch.no_grad()
@@ -326,35 +339,20 @@ class BLIP_Retrieval(BLIP_ITM):
         enqueue, negatives, one ITM pass over the B positive and 2B negative pairs, cross-entropy."""
         who = f"{type(self).__name__}.forward"
         # ---- refusals: before anything is launched or changed
-        require_cuda(image, who)
-        self._check_visual_input(image, who)
-        require_plain(self, who, "the loss forward", "its momentum towers and contrastive loss run on plain 16-bit operands")
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            raise NotImplementedError(f"{who}: world size {torch.distributed.get_world_size()} — the all-rank negatives and the "
-                                      "gathered queue update are not built (negative_all_rank coincides with the local form at "
-                                      "world size 1 only)")
+        self._refuse_unserved(image, who)
         B, dev = image.shape[0], image.device
         caption = list(caption)
         idx_host = torch.as_tensor(idx).detach().reshape(-1).cpu().long()
         if len(caption) != B or idx_host.numel() != B:
             raise ValueError(f"{who}: {B} images, {len(caption)} captions and {idx_host.numel()} idx entries")
-        if self.queue_size % B:
-            raise ValueError(f"{who}: queue_size={self.queue_size} is not a multiple of the batch size {B}")
-        if B > QUEUE_HEAD:
-            raise ValueError(f"{who}: batch size {B} exceeds the {QUEUE_HEAD} rows kept for the batch features")
+        self._refuse_batch(B, who)
         same = idx_host.view(-1, 1) == idx_host.view(1, -1)
         if negatives is None:
             lonely = same.all(1).nonzero()
             if lonely.numel():
                 raise ValueError(f"{who}: row {int(lonely[0])} has no admissible negative (every sample of the batch shares its idx)")
         else:
-            negatives = tuple(torch.as_tensor(n).detach().reshape(-1).cpu().long() for n in negatives)
-            for name, n in zip(("neg_image_of_text", "neg_text_of_image"), negatives):
-                if n.numel() != B or (n < 0).any() or (n >= B).any():
-                    raise ValueError(f"{who}: negatives: {name} must hold {B} indices in [0, {B})")
-                bad = same[torch.arange(B), n].nonzero()
-                if bad.numel():
-                    raise ValueError(f"{who}: negatives: {name}[{int(bad[0])}] names a sample of the same idx")
+            negatives = self._checked_negatives(negatives, same, who, "names a sample of the same idx")
         self.ensure_momentum_state()
         idx_dev = idx_host.to(dev)
 
@@ -374,8 +372,8 @@ class BLIP_Retrieval(BLIP_ITM):
 
         # ---- image-text contrastive loss (:123-141)
         image_store, text_store = self._key_store("image_queue"), self._key_store("text_queue")
-        loss_i2t = self._itc_direction(image_feat, image_feat_m, text_feat_m, text_store, alpha, temp).mean()
-        loss_t2i = self._itc_direction(text_feat, text_feat_m, image_feat_m, image_store, alpha, temp).mean()
+        loss_i2t = self._itc_direction(image_feat, image_feat_m, text_feat_m, text_store, alpha, temp)[0].mean()
+        loss_t2i = self._itc_direction(text_feat, text_feat_m, image_feat_m, image_store, alpha, temp)[0].mean()
         loss_ita = (loss_i2t + loss_t2i) / 2
         self._dequeue_and_enqueue(image_feat_m, text_feat_m, idx_dev)                        # :143-145
 
@@ -388,6 +386,46 @@ class BLIP_Retrieval(BLIP_ITM):
             neg_text = self._draw_negatives(sim_i2t, idx_dev, seed, 1)                        # a negative text for each image
         else:
             neg_image, neg_text = negatives[0].to(dev), negatives[1].to(dev)
+        vl_output, loss_itm = self._itm_loss(enc16, B, ids, lens, neg_image, neg_text)
+        if details is not None:
+            details.update(image_feat=image_feat, text_feat=text_feat, image_feat_m=image_feat_m, text_feat_m=text_feat_m,
+                           sim_i2t=sim_i2t, sim_t2i=sim_t2i, neg_image_of_text=neg_image, neg_text_of_image=neg_text,
+                           itm_logits=vl_output, loss_i2t=loss_i2t, loss_t2i=loss_t2i, temp=temp.clone())
+        return loss_ita.float(), loss_itm.float()
+
+    # ------------------------------------------------------------------ pieces of the loss forward (shared with BLIP_Pretrain)
+    def _refuse_unserved(self, image, who):
+        require_cuda(image, who)
+        self._check_visual_input(image, who)
+        require_plain(self, who, "the loss forward", "its momentum towers and contrastive loss run on plain 16-bit operands")
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise NotImplementedError(f"{who}: world size {torch.distributed.get_world_size()} — the all-rank negatives and the "
+                                      "gathered queue update are not built (negative_all_rank coincides with the local form at "
+                                      "world size 1 only)")
+
+    def _refuse_batch(self, B, who):
+        if self.queue_size % B:
+            raise ValueError(f"{who}: queue_size={self.queue_size} is not a multiple of the batch size {B}")
+        if B > QUEUE_HEAD:
+            raise ValueError(f"{who}: batch size {B} exceeds the {QUEUE_HEAD} rows kept for the batch features")
+
+    @staticmethod
+    def _checked_negatives(negatives, inadmissible, who, why):
+        """negatives = (neg_image_of_text, neg_text_of_image) -> two int64 host tensors [B]; ``inadmissible`` bool [B,B]."""
+        B = inadmissible.shape[0]
+        negatives = tuple(torch.as_tensor(n).detach().reshape(-1).cpu().long() for n in negatives)
+        for name, n in zip(("neg_image_of_text", "neg_text_of_image"), negatives):
+            if n.numel() != B or (n < 0).any() or (n >= B).any():
+                raise ValueError(f"{who}: negatives: {name} must hold {B} indices in [0, {B})")
+            bad = inadmissible[torch.arange(B), n].nonzero()
+            if bad.numel():
+                raise ValueError(f"{who}: negatives: {name}[{int(bad[0])}] {why}")
+        return negatives
+
+    def _itm_loss(self, enc16, B, ids, lens, neg_image, neg_text):
+        """One ITM pass over the B positive and 2B negative pairs (:148-248) -> (logits f32 [3B,2], the two-class cross-entropy).
+        ids / lens: the B captions as tokenised (host); the first id becomes [ENC]."""
+        dev = enc16.device
         enc_ids = ids.clone()
         enc_ids[:, 0] = self.tokenizer.enc_token_id                                          # :148-149
         ar = torch.arange(B, device=dev)
@@ -404,12 +442,7 @@ class BLIP_Retrieval(BLIP_ITM):
         else:
             vl_output = self.itm_pairs(enc16, B, enc_ids, lens, image_index=pair_image, pair_text=pair_text)
         itm_labels = torch.cat([torch.ones(B, dtype=torch.long), torch.zeros(2 * B, dtype=torch.long)]).to(dev)
-        loss_itm = nn.functional.cross_entropy(vl_output, itm_labels)                        # :246-248
-        if details is not None:
-            details.update(image_feat=image_feat, text_feat=text_feat, image_feat_m=image_feat_m, text_feat_m=text_feat_m,
-                           sim_i2t=sim_i2t, sim_t2i=sim_t2i, neg_image_of_text=neg_image, neg_text_of_image=neg_text,
-                           itm_logits=vl_output, loss_i2t=loss_i2t, loss_t2i=loss_t2i, temp=temp.clone())
-        return loss_ita.float(), loss_itm.float()
+        return vl_output, nn.functional.cross_entropy(vl_output, itm_labels)                # :246-248
 
 
 class BLIP_Retrieval_Video(BLIP_Retrieval):

@@ -82,6 +82,25 @@ def split_sentences(texts, do_sentence_tokenization=True):
         return []
     if not do_sentence_tokenization:
         return [t.replace("\n", ". ").strip() for t in texts]
+    nlp = sentence_splitter()
+    out = []
+    for t in texts:
+        for sent in sentences_of(nlp, t.replace("\n", ". ")):
+            if len(sent) > 3:
+                out.append(sent.strip())
+    return out
+
+
+def sentences_of(nlp, text):
+    """The sentence texts of ``text`` under a splitter: a spaCy pipeline (``doc.sents``) or "naive" (plain '. ' splitting)."""
+    if nlp == "naive":
+        return text.split(". ")
+    return [sent.text for sent in nlp(text).sents]
+
+
+def sentence_splitter():
+    """The splitter ``split_sentences`` uses, loaded once: spaCy's en_core_web_sm, or "naive" when that is missing and
+    VIDIL_SENTENCE_SPLIT=naive asks for it (anything else raises)."""
     nlp = split_sentences.__dict__.get("_nlp")
     if nlp is None:
         try:
@@ -100,16 +119,7 @@ def split_sentences(texts, do_sentence_tokenization=True):
                           "(VIDIL_SENTENCE_SPLIT=naive) — sentence boundaries may differ from the reference")
             nlp = "naive"
         split_sentences._nlp = nlp
-    out = []
-    for t in texts:
-        if nlp == "naive":
-            sents = t.replace("\n", ". ").split(". ")
-        else:
-            sents = [sent.text for sent in nlp(t.replace("\n", ". ")).sents]
-        for sent in sents:
-            if len(sent) > 3:
-                out.append(sent.strip())
-    return out
+    return nlp
 
 
 _REQUIRED_KEYS = ("caption", "filter")
