@@ -171,7 +171,20 @@ typedef struct vidil_gemm_args {
 
 /* replaces: nn.Linear calls of models/vit.py:35-41,72,84; models/med.py:153-171,
  * 236,301,314,512,534; timm PatchEmbed conv (models/vit.py:144-145,182) as an
- * im2col-free GEMM; HF CLIP q/k/v/out/fc1/fc2/projection Linears. */
+ * im2col-free GEMM; HF CLIP q/k/v/out/fc1/fc2/projection Linears.
+ *
+ * Pinned by tests/test_gemm_forms_gpu.py (16-bit operands; every kernel form and tile height behind this call, split_k
+ * included): a launch writes the elements the epilogue's map above names for rows < M and columns < N, and NOTHING else —
+ *   EPI_F16 / EPI_F32: not the columns N .. ldo - 1 of a row, not a row >= M;
+ *   EPI_PATCH: not the class rows b * (tpi + 1), not the columns N .. ldo - 1;
+ *   EPI_HEADS: in Q only token rows 0 .. T - 1 of the Tq_cap of an image, in K / V only rows t_off .. t_off + T - 1 of Tk_cap
+ *     (fragment-tiled: only those keys' slots of a tile), in V^T only the columns vt(t_off .. t_off + T - 1) of NP;
+ *   EPI_ARENA: only positions t_off .. t_off + T - 1 and slots b * slot_stride, b < M / T, of the arena_rows;
+ * so callers may keep live data in the capacity rows, padding columns, other positions / slots and in neighbouring
+ * allocations.  The padding columns of A (lda > K) may hold anything, NaNs included (observed by the test).  So may the memory
+ * behind the last rows of A and W, as far as a staging load reaches it at all: row m of A feeds row m of the product only, row n
+ * of W column n only, and rows >= M / columns >= N are never stored (this follows from the masking; the test keeps one tile of
+ * NaN rows there).  With operands whose products and sums are exact in f32 the result is exact, whichever form serves the call. */
 int vidil_gemm(const vidil_gemm_args* args, void* stream);
 /* (ABI 12) Per CALL: 1 when vidil_gemm would run `args` (split_k != 0) in the K-loop form — planes 0 / 1 of the A rows are
  * all it reads, so their producer may be run with VIDIL_DT_SPLIT2 / out16_split3 = 2 / out_mode 3 —, 0 when it would run the plain
