@@ -260,6 +260,28 @@ int vidil_layernorm(const float* x, int64_t x_stride, const float* gamma,
 /* the fp8 tower mode feeds the attention output straight to the proj GEMM),  */
 /* or dtype | VIDIL_DT_SPLIT3: row = three planes [hi | lo | hi] of ldo/3     */
 /* columns each (ldo a multiple of 24, ldo/3 >= H*64).                        */
+/* pinned by tests/test_attention_forms_gpu.py (the staged kernel in all of    */
+/* its instantiations, single chunk and 224-key chunks, and the direct kernel  */
+/* in both K/V layouts; every unit form and output form, against fp64):        */
+/*  - a row with no admissible key (kv_len[b] == 0, or causal with             */
+/*    t + causal_off + 1 <= 0) is written as zeros - hi and lo alike; kv_len   */
+/*    above Nk means Nk.                                                       */
+/*  - query batches that no group of group_start names are not written at all; */
+/*    nor are the columns behind H*64 of a row or plane, nor rows >= Bq*Nq.    */
+/*    K / V rows Nk .. Tk_cap-1, V^T columns behind the 16-key block that      */
+/*    holds key Nk-1, tile slots past Nk and Q rows Nq .. Tq_cap-1 may hold    */
+/*    anything, NaNs included.                                                 */
+/*  - causal_off may be negative (the first -causal_off rows then have no key).*/
+/*  - `out` needs the alignment of its element type only: rows that are not    */
+/*    16-byte aligned take the narrow store path of the same kernel.           */
+/*  - up to 768 keys a row's bits depend on its Q row, the unit's K / V and    */
+/*    its key limit alone, within one kernel family: the staged kernel gives   */
+/*    the same bits for a unit launched alone, with its query batches in any   */
+/*    order, as kv_index batches of more than 32 rows, with 4 or 8 waves and   */
+/*    one or two rounds of row blocks, and so does the streamed tower kernel;  */
+/*    the direct kernel for a unit launched alone and for kv_tiled 0 / 1 / 2.  */
+/*    (The two families round differently: the staged kernel keeps a lazy      */
+/*    softmax reference, the direct kernel the exact running maximum.)         */
 /* replaces: models/vit.py:75-83; models/med.py:178-220 (self, cross, cached);*/
 /* HF CLIPAttention.                                                          */
 /* ------------------------------------------------------------------------ */

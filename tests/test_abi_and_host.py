@@ -87,6 +87,21 @@ def test_argument_validation_without_a_gpu():
     assert b"multiple of 32" in lib.vidil_last_error()
     assert lib.vidil_attention(16, 16, 16, 16, None, None, None, 0, 0, 40, 12, 1, 197, 1, 224, 0, 40, 0, 0, 768, 1, 0, 0, None) == -1
     assert b"at most 32 query rows" in lib.vidil_last_error()
+    # the edges of the staged / direct kernels' contract (tests/test_attention_forms_gpu.py covers what is inside it): 769 keys
+    # with at most 32 rows per unit on plain K / V; row-major V (NP == 0) with at most 32 rows; a V^T stride that is no multiple
+    # of 16; group_start together with kv_index; fp8 rows at ldo % 16 != 0; split3 rows at ldo % 24 != 0
+    assert lib.vidil_attention(16, 16, 16, 16, None, None, None, 0, 0, 1, 12, 4, 769, 4, 769, 784, 1, 0, 0, 768, 0, 0, 0, None) == -3
+    assert b"Nk=769 > 768 not supported" in lib.vidil_last_error()
+    assert lib.vidil_attention(16, 16, 16, 16, None, None, None, 0, 0, 1, 12, 4, 64, 4, 64, 0, 1, 0, 0, 768, 0, 0, 0, None) == -1
+    assert b"row-major V (NP == 0) needs more than 32 query rows" in lib.vidil_last_error()
+    assert lib.vidil_attention(16, 16, 16, 16, None, None, None, 0, 0, 1, 12, 40, 64, 40, 64, 72, 1, 0, 0, 768, 0, 0, 0, None) == -1
+    assert b"NP=72 must be a multiple of 16" in lib.vidil_last_error()
+    assert lib.vidil_attention(16, 16, 16, 16, None, 16, 16, 1, 1, 1, 12, 40, 64, 40, 64, 64, 1, 0, 0, 768, 0, 0, 0, None) == -1
+    assert b"group_start and kv_index are mutually exclusive" in lib.vidil_last_error()
+    assert lib.vidil_attention(16, 16, 16, 16, None, None, None, 0, 0, 1, 1, 40, 64, 40, 64, 64, 1, 0, 0, 72, 0, 0, 2, None) == -1
+    assert b"out_dtype" in lib.vidil_last_error()
+    assert lib.vidil_attention(16, 16, 16, 16, None, None, None, 0, 0, 1, 1, 40, 64, 40, 64, 64, 1, 0, 0, 200, 0, 0, 0x100, None) == -1
+    assert b"split3 output needs ldo=200" in lib.vidil_last_error()
     assert lib.vidil_scan_topk_ws_bytes(128, 42784, 5) > 0
     # the parity mode's f32 attention: 16-byte aligned rows / head offsets, one query row per batch in the arena form
     a = _lib.AttnF32Args()
