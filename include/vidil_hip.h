@@ -623,7 +623,41 @@ int vidil_sample_top_k_top_p(const float* logits, int32_t* seqs, int32_t* done,
 /* 16-byte aligned, vidil_scan_topk_ws_bytes(NF, NCpad, 0) bytes.  No ABI     */
 /* bump: topk == 0 was VIDIL_EINVAL for every caller built so far, and no     */
 /* signature or struct changes.                                               */
+/*                                                                            */
+/* topk == VIDIL_SCAN_FORM_GRAD is the GRADIENT form of that loss: the mirror */
+/* of topk == 0, which reads the keys once more and writes no score matrix.   */
+/* NF must be even, P = NF/2 pairs, D % 8 == 0 and D <= 256 (16 x D           */
+/* accumulators live in registers; a larger D is VIDIL_EINVAL before any      */
+/* launch; the other forms keep D <= 1024).  The operands are packed into the */
+/* existing parameters:                                                       */
+/*   img       f32: the 2P rows [2P,D] (value rows, then weight rows, as for  */
+/*             topk == 0), followed by 5P constants [5,P] = lv, lw, cv, cw    */
+/*             and the bits of an i32 h: the pair's HARD class, a class index */
+/*             within the FIRST segment, or -1 for none;                      */
+/*   txt, D, ncat and the segments as above;                                  */
+/*   out_score f32: G [P,D], followed by T [P] and C [P]; 16-byte aligned;    */
+/*   out_index must be non-null and is not written.                           */
+/* With v_j = img[p]·txt[j] and w_j = img[P+p]·txt[j] (the chains of          */
+/* topk == 0, bit for bit) over the classes j of ALL segments together:       */
+/*   c_j    = cv[p]·exp(v_j - lv[p]) - cw[p]·exp(w_j - lw[p])                 */
+/*   G[p,:] = sum_j c_j · txt[j,:]        T[p] = sum_j exp(v_j - lv[p]) · v_j */
+/*   C[p]   = sum_j c_j                                                       */
+/* where the sums of G and C (not of T) leave the class h[p] out.  With the   */
+/* loss's positive as h, G - C · txt[h] = sum_{j != h} c_j (txt[j] - txt[h])  */
+/* is the gradient row without ever forming the dominant term c_h · txt[h].   */
+/* Nothing behind those extents is written and rows between segments never    */
+/* reach a result.  A segment is cut into key splits of 1024 classes; a       */
+/* workgroup of four waves owns 16 pairs and one split, wave w takes the      */
+/* split's class tiles w, w + 4, ..., the four waves' sums are added in wave  */
+/* order and a second kernel adds the splits in split order (no atomics): the */
+/* cut depends on the segment lengths alone, so a pair's bits do not depend   */
+/* on P, its position or the rest of the launch.  partial must be 16-byte     */
+/* aligned, vidil_scan_topk_ws_bytes(NF, NCpad, VIDIL_SCAN_FORM_GRAD) bytes   */
+/* (one partial row, T and C per split and pair: 17.2 MB at P = 256,          */
+/* NC = 58,112, where ONE [P, NC] f32 matrix is 59.5 MB).  No ABI bump: the   */
+/* was VIDIL_EINVAL ("topk=-2 (1..8)") for every caller built so far.         */
 /* ------------------------------------------------------------------------ */
+#define VIDIL_SCAN_FORM_GRAD (-2)
 int64_t vidil_scan_topk_ws_bytes(int32_t NF, int32_t NCpad, int32_t topk);
 int vidil_scan_topk(const float* img, const float* txt, int32_t NF, int32_t D,
                     int32_t ncat, const int32_t* seg_start_host,

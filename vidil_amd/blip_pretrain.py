@@ -5,7 +5,8 @@
 One ViT pass serves three losses:
 
   * ITC — the soft-target contrastive loss over batch + queue of ``BLIP_Retrieval`` (``_itc_direction``: the exact-f32 scan's
-    stats form), with the class's momentum towers, EMA and queues; the pointer buffer is ``queue_ptr`` and there are no sample ids;
+    stats form), with the class's momentum towers, EMA and queues; the pointer buffer is ``queue_ptr`` and there are no sample ids.
+    ``grads=`` returns its gradients with respect to the online features and ``temp`` (vidil_amd/losses.py), the only backward so far;
   * ITM — one pass over the B positive and 2B hard-negative pairs (``BLIP_Retrieval._itm_loss``).  Unlike the retrieval class the
     weights of a draw come from the student-against-MOMENTUM similarities the contrastive loss already formed (the first B columns
     of sim_t2i / sim_i2t, :155-158): softmax + 1e-4, diagonal zeroed, no id masking;
@@ -96,8 +97,8 @@ class BLIP_Pretrain(BLIP_Retrieval):
         return self.packed()
 
     @torch.no_grad()
-    def forward(self, image, caption, alpha, *, negatives=None, seed=None, details=None, timings=None):
-        """models/blip_pretrain.py:97-212 (BLIP_Pretrain_Video: :328-452), forward only -> (loss_ita, loss_itm, loss_lm), 0-dim
+    def forward(self, image, caption, alpha, *, negatives=None, seed=None, details=None, timings=None, grads=None):
+        """models/blip_pretrain.py:97-212 (BLIP_Pretrain_Video: :328-452) -> (loss_ita, loss_itm, loss_lm), 0-dim
         f32 device tensors.  image f32 [B,3,S,S] (video: [B,N,3,S,S]); caption: B strings; alpha: float.
         negatives = (neg_image_of_text, neg_text_of_image), int [B] each: given draws instead of this library's own Philox draws
         (seed, default 0).  details (dict) receives the four features, ``sim_i2t`` / ``sim_t2i`` (the student rows against the
@@ -105,6 +106,9 @@ class BLIP_Pretrain(BLIP_Retrieval):
         ``lm_count`` [B] and the per-target ``lm_lp_label`` / ``lm_lp_mean`` / ``lm_caption``, ``loss_i2t`` / ``loss_t2i``, ``temp``.
         timings (dict): seconds per phase from HIP events (video.phase_timer; every phase is synchronised) — ``vit``, ``text``,
         ``ema``, ``repack``, ``momentum``, ``itc``, ``itm``, ``lm``.
+        grads (dict) receives ``image_feat``, ``text_feat`` (f32 [B, embed_dim]) and ``temp`` (0-dim f32): the gradients of
+        ``loss_ita`` only with respect to the online features and the temperature (partial gradients of the total loss; see
+        ``BLIP_Retrieval.loss_forward``).  Losses, ``details`` and every state change are the bits of the call without it.
         Order of effects as in the reference: temp clamp, online features, EMA, momentum features, ITC loss, enqueue, negatives,
         the ITM pass, the LM pass."""
         who = f"{type(self).__name__}.forward"
@@ -142,11 +146,8 @@ class BLIP_Pretrain(BLIP_Retrieval):
         t0 = lap("momentum", t0)
 
         # ---- image-text contrastive loss (:123-138) and the enqueue (:140)
-        image_store, text_store = self._key_store("image_queue"), self._key_store("text_queue")
-        rows_i2t, sim_i2t = self._itc_direction(image_feat, image_feat_m, text_feat_m, text_store, alpha, temp)
-        rows_t2i, sim_t2i = self._itc_direction(text_feat, text_feat_m, image_feat_m, image_store, alpha, temp)
-        loss_i2t, loss_t2i = rows_i2t.mean(), rows_t2i.mean()
-        loss_ita = (loss_i2t + loss_t2i) / 2
+        loss_ita, loss_i2t, loss_t2i, sim_i2t, sim_t2i = self._itc_losses(image_feat, text_feat, image_feat_m, text_feat_m, alpha,
+                                                                          temp, grads)
         self._dequeue_and_enqueue(image_feat_m, text_feat_m)
         t0 = lap("itc", t0)
 
@@ -182,8 +183,8 @@ class BLIP_Pretrain_Video(BLIP_Pretrain, BLIP_Retrieval_Video):
     # (the visual side — frame tokens, the mean-of-frames feature, the token limit — is BLIP_Retrieval_Video's, inherited)
 
     @torch.no_grad()
-    def forward(self, video, caption, alpha, *, negatives=None, seed=None, details=None, timings=None):
-        return super().forward(video, caption, alpha, negatives=negatives, seed=seed, details=details, timings=timings)
+    def forward(self, video, caption, alpha, *, negatives=None, seed=None, details=None, timings=None, grads=None):
+        return super().forward(video, caption, alpha, negatives=negatives, seed=seed, details=details, timings=timings, grads=grads)
 
 
 def _from_pretrained(model, pretrained):

@@ -16,7 +16,8 @@ and, for the video-level retrieval evaluation (eval_retrieval_video.py; vidil_am
   * ``video_features_u8(frames)``  -> the tokens of every frame, a video's N*T rows contiguous, and
     ``normalize(mean_frames(vision_proj(cls)))``                       (eval_retrieval_video.py:61-69)
 
-The loss forward (forward only; models/blip_retrieval.py:76-251 and, for ``BLIP_Retrieval_Video``, :350-518):
+The loss forward (models/blip_retrieval.py:76-251 and, for ``BLIP_Retrieval_Video``, :350-518; forward only, except that
+``grads=`` returns the gradients of ``loss_ita`` with respect to the online features and ``temp``: vidil_amd/losses.py):
 ``forward(image | video, caption, alpha=, idx=) -> (loss_ita, loss_itm)``.  Its state — the momentum towers
 ``visual_encoder_m / vision_proj_m / text_encoder_m / text_proj_m`` and the queues ``image_queue / text_queue / idx_queue /
 ptr_queue`` under the reference's names and shapes — is opt-in: ``momentum_state=True`` in the constructor, or
@@ -43,13 +44,14 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
+from . import losses
 from .blip import CLIP_MEAN, CLIP_STD, load_checkpoint
 from .blip_itm import ITM_MAX_LENGTH, BLIP_ITM
 from .packing import require_cuda, v32, w16
 from .tokenizer import refuse_synthetic_with_checkpoint
 from .video import frame_tokens, group_table, require_plain
 
-QUEUE_HEAD = 512     # rows of a key buffer in front of the queue (a multiple of 32): a call's batch features live in rows [0, B)
+QUEUE_HEAD = losses.QUEUE_HEAD     # rows of a key buffer in front of the queue: a call's batch features live in rows [0, B)
 MOMENTUM_PAIRS = (("visual_encoder", "visual_encoder_m"), ("vision_proj", "vision_proj_m"),
                   ("text_encoder", "text_encoder_m"), ("text_proj", "text_proj_m"))       # models/blip_retrieval.py:53-57
 _MODE_FLAGS = ("_compute_dtype", "_parity", "_parity_attn")
@@ -265,16 +267,18 @@ class BLIP_Retrieval(BLIP_ITM):
         return self.itm_pairs(y16, n_images, ids, lens, group_start=group_start, max_group=max_group)[:, 1].contiguous()
 
     @torch.no_grad()
-    def forward(self, image, caption, match_head="itm", *, alpha=None, idx=None, negatives=None, seed=None, details=None):
+    def forward(self, image, caption, match_head="itm", *, alpha=None, idx=None, negatives=None, seed=None, details=None,
+                grads=None):
         """Without ``alpha`` / ``idx``: models/blip_itm.py:41-67 call shape; 'itc' returns image_feat @ text_feat.t() [F,F].
         With both (keywords, as train_retrieval.py passes them): the reference's training forward, models/blip_retrieval.py:76-251
-        -> (loss_ita, loss_itm), 0-dim f32 device tensors (see ``loss_forward``)."""
+        -> (loss_ita, loss_itm), 0-dim f32 device tensors (see ``loss_forward``, also for ``grads=``)."""
         if alpha is not None or idx is not None:
             if alpha is None or idx is None:
                 raise TypeError(f"{type(self).__name__}.forward: the loss forward needs both alpha= and idx=")
-            return self.loss_forward(image, caption, alpha, idx, negatives=negatives, seed=seed, details=details)
-        if negatives is not None or seed is not None or details is not None:
-            raise TypeError(f"{type(self).__name__}.forward: negatives= / seed= / details= belong to the loss forward (alpha=, idx=)")
+            return self.loss_forward(image, caption, alpha, idx, negatives=negatives, seed=seed, details=details, grads=grads)
+        if negatives is not None or seed is not None or details is not None or grads is not None:
+            raise TypeError(f"{type(self).__name__}.forward: negatives= / seed= / details= / grads= belong to the loss forward "
+                            "(alpha=, idx=)")
         if match_head == "itm":
             return super().forward(image, caption, match_head)
         if match_head != "itc":
@@ -302,16 +306,21 @@ class BLIP_Retrieval(BLIP_ITM):
         against the batch's momentum keys over temp — the block the diagonal is read from).  a, a_m: the student and the
         momentum rows [B, D] (unit norm); keys_m: the other modality's momentum batch features, written to rows [0, B) of its key
         store, whose queue segment starts at QUEUE_HEAD."""
-        B = a.shape[0]
-        store[:B] = keys_m
-        q, q_m = (a / temp).contiguous(), (a_m / temp).contiguous()
-        st, _ = K.scan_softmax_stats(q, q_m, store, [0, QUEUE_HEAD], [B, self.queue_size])         # [B, 2, 5]
-        m, mw = st[..., 0].amax(1, keepdim=True), st[..., 2].amax(1, keepdim=True)
-        ev, ew = torch.exp(st[..., 0] - m), torch.exp(st[..., 2] - mw)
-        lse = m[:, 0] + torch.log((st[..., 1] * ev).sum(1))
-        soft = (st[..., 4] * ew).sum(1) / (st[..., 3] * ew).sum(1)                              # sum_j softmax(m)_j s_j
-        block = K.scan_scores(q, store[:B])
-        return lse - alpha * soft - (1.0 - alpha) * block.diagonal(), block
+        return losses.ItcDirection.apply(a, a_m, keys_m, store, alpha, temp, self.queue_size)
+
+    def _itc_losses(self, image_feat, text_feat, image_feat_m, text_feat_m, alpha, temp, grads=None):
+        """Both directions (:123-141) -> (loss_ita, loss_i2t, loss_t2i, sim_i2t, sim_t2i), the last two the [B,B] blocks of
+        ``_itc_direction``.  grads (dict) receives the gradients of loss_ita only, with respect to ``image_feat``, ``text_feat``
+        and ``temp`` — computed here, before the enqueue changes the keys the loss was taken over; the values returned are the
+        same bits with and without it."""
+        image_store, text_store = self._key_store("image_queue"), self._key_store("text_queue")
+        if grads is not None:
+            return losses.itc_terms_with_grads(grads, image_feat, text_feat, image_feat_m, text_feat_m, image_store, text_store,
+                                               temp, alpha, self.queue_size)
+        rows_i2t, sim_i2t = self._itc_direction(image_feat, image_feat_m, text_feat_m, text_store, alpha, temp)
+        rows_t2i, sim_t2i = self._itc_direction(text_feat, text_feat_m, image_feat_m, image_store, alpha, temp)
+        loss_i2t, loss_t2i = rows_i2t.mean(), rows_t2i.mean()
+        return (loss_i2t + loss_t2i) / 2, loss_i2t, loss_t2i, sim_i2t, sim_t2i
 
     def _draw_negatives(self, sim, idx, seed, stream):
         """One negative column per row of sim f32 [B,B] (already / temp): weights = softmax with same-idx entries zeroed
@@ -330,12 +339,17 @@ class BLIP_Retrieval(BLIP_ITM):
         return (c <= (u * c[:, -1])[:, None]).sum(1).clamp_(max=B - 1)
 
     @torch.no_grad()
-    def loss_forward(self, image, caption, alpha, idx, *, negatives=None, seed=None, details=None):
-        """models/blip_retrieval.py:76-251 (BLIP_Retrieval_Video: :350-518), forward only -> (loss_ita, loss_itm).
+    def loss_forward(self, image, caption, alpha, idx, *, negatives=None, seed=None, details=None, grads=None):
+        """models/blip_retrieval.py:76-251 (BLIP_Retrieval_Video: :350-518) -> (loss_ita, loss_itm).
         image f32 [B,3,S,S] (video: [B,N,3,S,S]); caption: B strings; alpha: float; idx: int [B] (the sample ids whose equals
         are no negatives of each other).  negatives = (neg_image_of_text, neg_text_of_image), int [B] each: given draws instead
         of this library's own (seed, default 0).  details (dict) receives the features, the in-batch similarities, the draws and
-        the ITM logits.  Order of effects as in the reference: temp clamp, online features, EMA, momentum features, ITC loss,
+        the ITM logits.  grads (dict) receives ``image_feat``, ``text_feat`` (f32 [B, embed_dim]) and ``temp`` (0-dim f32): the
+        gradients of ``loss_ita`` only with respect to the online features and the temperature — what the reference's
+        ``loss_ita.backward()`` leaves at those nodes, partial gradients of the total loss; nothing is written to a parameter's
+        ``.grad``, and losses, ``details`` and every state change are the bits of the call without it.  The projection heads, the
+        text stack, the ViT and ``loss_itm`` have no backward yet.
+        Order of effects as in the reference: temp clamp, online features, EMA, momentum features, ITC loss,
         enqueue, negatives, one ITM pass over the B positive and 2B negative pairs, cross-entropy."""
         who = f"{type(self).__name__}.forward"
         # ---- refusals: before anything is launched or changed
@@ -371,10 +385,7 @@ class BLIP_Retrieval(BLIP_ITM):
         text_feat_m = self._project_cls(h16, B, t_eff, p["tp_w_m"], p["tp_b_m"])            # :114-116
 
         # ---- image-text contrastive loss (:123-141)
-        image_store, text_store = self._key_store("image_queue"), self._key_store("text_queue")
-        loss_i2t = self._itc_direction(image_feat, image_feat_m, text_feat_m, text_store, alpha, temp)[0].mean()
-        loss_t2i = self._itc_direction(text_feat, text_feat_m, image_feat_m, image_store, alpha, temp)[0].mean()
-        loss_ita = (loss_i2t + loss_t2i) / 2
+        loss_ita, loss_i2t, loss_t2i, _, _ = self._itc_losses(image_feat, text_feat, image_feat_m, text_feat_m, alpha, temp, grads)
         self._dequeue_and_enqueue(image_feat_m, text_feat_m, idx_dev)                        # :143-145
 
         # ---- hard negatives (:199-224) and the matching loss (:148-248)
@@ -451,8 +462,8 @@ class BLIP_Retrieval_Video(BLIP_Retrieval):
     BertModel.LONG_KEYS keys its pairs go image-major through ``group_start``)."""
 
     @torch.no_grad()
-    def forward(self, video, caption, alpha, idx, *, negatives=None, seed=None, details=None):
-        return self.loss_forward(video, caption, alpha, idx, negatives=negatives, seed=seed, details=details)
+    def forward(self, video, caption, alpha, idx, *, negatives=None, seed=None, details=None, grads=None):
+        return self.loss_forward(video, caption, alpha, idx, negatives=negatives, seed=seed, details=details, grads=grads)
 
     def _check_visual_input(self, video, who):
         if video.dim() != 5 or video.shape[2] != 3:

@@ -26,6 +26,11 @@
 // weighted sum) states are merged in the same fixed order: 8 lists per row
 // through LDS, then the chunks of a category in chunk order (one wave per
 // pair and category: stats_merge_kernel).  No atomics.
+//
+// topk == VIDIL_SCAN_FORM_GRAD is the gradient form of that loss (grad_kernel,
+// grad_merge_kernel below): the same 16 + 16 rows and the same score chains,
+// the softmax-difference coefficient in registers, and a second contraction
+// with the keys on v_mfma_f32_16x16x4_f32 into a [16 pairs x D] accumulator.
 #include "common.h"
 
 namespace {
@@ -329,6 +334,186 @@ __global__ __launch_bounds__(64) void stats_merge_kernel(const ScanP p, int32_t*
   }
 }
 
+// ---- gradient form (topk == VIDIL_SCAN_FORM_GRAD): the mirror of the paired softmax statistics ------------------------------
+// Per pair, with v_j / w_j the value and the weight row's scores (the chains of stats_kernel, bit for bit) over the classes of
+// ALL segments:  c_j = cv exp(v_j - lv) - cw exp(w_j - lw),  G = sum_j c_j keys[j,:],  T = sum_j exp(v_j - lv) v_j,  C = sum_j c_j;
+// a pair's HARD class h (a class of the first segment, or -1) is left out of G and C: the loss's gradient row is then
+// G - C keys[h] = sum_{j != h} c_j (keys[j] - keys[h]), which never forms and cancels the dominant term c_h keys[h].
+// A workgroup owns 16 pairs and one key split: GT consecutive class tiles of one segment, so the splits depend on the segment
+// lengths alone.  A wave takes the split's tiles wave, wave + 4, ...: the 32x32x2 score MFMA as in stats_kernel, the coefficient
+// in registers, then G[16 x D] += c[16 x 32] · keys[32 x D] on the 16x16x4 f32 MFMA.  Its A operand is the coefficient the lane
+// already holds (lanes l and l ^ 16 form the same c; k-step s of lane group g = lane >> 4 takes class (s&3) + 16(s>>2) +
+// 8(g&1) + 4(g>>1) of the tile, which is register (s&3) + 8(s>>2) + 4(g&1) of the score tile), so no coefficient moves between
+// lanes or through LDS.  Its B operand is the key tile read a second time, 16 lanes to 256 contiguous bytes of a key row (the
+// tile is 32 KB at D = 256 and was read by this wave just before; four waves' tiles beside the 16 + 16 staged rows exceed the
+// 160 KB of LDS by 2.5 KB, so the second read goes to the caches, not to an LDS copy).  Output tile t of column group q holds
+// column 64q + 4(lane & 15) + t: one b128 load feeds four MFMAs and a lane's four accumulator tiles are four adjacent columns.
+// The four waves' accumulators are added in wave order through LDS, the partial goes to the workspace, and grad_merge_kernel
+// adds the splits in split order.  No atomics.
+constexpr int GT = 32;  // class tiles per key split (1024 classes)
+constexpr int GRAD_DMAX = 256;  // 16 x 256 accumulators = 64 registers per lane
+
+struct GradP {
+  const float* rows;    // [2P][D]: value rows, then weight rows
+  const float* consts;  // [5][P]: lv, lw, cv, cw, and the bits of the i32 hard class (in segment 0; -1: none)
+  const float* keys;
+  int P, Ppad, D, ncat, nsplits;
+  int seg_start[MAXCAT], seg_len[MAXCAT];
+  int split_prefix[MAXCAT + 1];  // splits before segment c
+  float* part_g;  // [nsplits][Ppad][D]
+  float* part_t;  // [nsplits][Ppad]
+  float* part_c;  // [nsplits][Ppad]
+};
+
+template <int NQ>  // column groups of 64: D <= 64 NQ
+__global__ __launch_bounds__(256) void grad_kernel(const GradP p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int D = p.D, P = p.P;
+  const int FROW = D + 4;
+  float* Fs = (float*)smem;  // [32][FROW]: rows 0..15 value rows, 16..31 their weight rows; reused for the wave merge
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hi = lane >> 5, l31 = lane & 31, l15 = lane & 15, g = lane >> 4;
+  const int split = blockIdx.x, ptile = blockIdx.y;
+
+  int cat = 0;
+#pragma unroll
+  for (int c = 1; c < MAXCAT; ++c)
+    if (c < p.ncat && split >= p.split_prefix[c]) cat = c;
+  const int tile0 = (split - p.split_prefix[cat]) * GT;
+  const int seg_len = p.seg_len[cat];
+  const int ntiles_cat = (seg_len + 31) / 32;
+  const float* txt = p.keys + (size_t)p.seg_start[cat] * D;
+
+  {
+    const int vec_per_row = D / 4;
+    for (int q = tid; q < 32 * vec_per_row; q += 256) {
+      const int r = q / vec_per_row, c = q - r * vec_per_row;
+      const int pair = ptile * 16 + (r & 15);
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (pair < P) v = *(const f32x4*)(p.rows + (size_t)((r >> 4) * P + pair) * D + c * 4);
+      *(f32x4*)(Fs + r * FROW + c * 4) = v;
+    }
+  }
+  // the lane's pair: its four constants (a pair past P has zero rows and zero coefficients)
+  const int pair = ptile * 16 + l15;
+  float lv = 0.f, lw = 0.f, cv = 0.f, cw = 0.f;
+  int hard = -1;
+  if (pair < P) {
+    lv = p.consts[pair]; lw = p.consts[P + pair]; cv = p.consts[2 * P + pair]; cw = p.consts[3 * P + pair];
+    hard = __float_as_int(p.consts[4 * P + pair]);
+  }
+  if (cat != 0) hard = -1;  // the hard class is a class of the first segment
+  __syncthreads();
+
+  f32x4 G[NQ * 4];
+#pragma unroll
+  for (int i = 0; i < NQ * 4; ++i) G[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float T = 0.f, C = 0.f;
+
+  const float* frow = Fs + l31 * FROW + 4 * hi;
+  const bool is_value = l31 < 16;
+  for (int tt = wave; tt < GT; tt += 4) {
+    const int tile = tile0 + tt;
+    if (tile >= ntiles_cat) break;
+    const int cls = tile * 32 + l31;
+    const int cls_ld = cls < seg_len ? cls : seg_len - 1;
+    const float* trow = txt + (size_t)cls_ld * D + 4 * hi;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll 4
+    for (int c = 0; c < D / 8; ++c) {
+      const f32x4 a = *(const f32x4*)(trow + c * 8);
+      const f32x4 b = *(const f32x4*)(frow + c * 8);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc, 0, 0, 0);
+    }
+    // acc[r]: class = tile*32 + (r&3) + 8*(r>>2) + 4*hi ; row = lane&31 ; the partner row's score sits in lane ^ 16.
+    // Lanes l and l ^ 16 form the same coefficient of pair lane & 15 from (v, w) in the same order.
+    f32x16 coef;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c2 = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      const float y = __shfl_xor(acc[r], 16);
+      const float v = is_value ? acc[r] : y, w = is_value ? y : acc[r];
+      const float ev = expf(v - lv), ew = expf(w - lw);
+      const bool live = c2 < seg_len;
+      coef[r] = live && c2 != hard ? cv * ev - cw * ew : 0.f;  // the hard class is left out of G and C, not of T
+      C += coef[r];
+      T += live ? ev * v : 0.f;
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int rs = (s & 3) + 8 * (s >> 2);
+      const float a = (g & 1) ? coef[rs + 4] : coef[rs];
+      const int j = tile * 32 + (s & 3) + 16 * (s >> 2) + 8 * (g & 1) + 4 * (g >> 1);
+      const float* krow = txt + (size_t)(j < seg_len ? j : seg_len - 1) * D + 4 * l15;  // a masked class has a == 0
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        f32x4 b = {0.f, 0.f, 0.f, 0.f};
+        if (64 * q + 4 * l15 < D) b = *(const f32x4*)(krow + 64 * q);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) G[q * 4 + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[t], G[q * 4 + t], 0, 0, 0);
+      }
+    }
+  }
+
+  // ---- add the four waves' accumulators in wave order; T: the 8 (wave, half) sums of a pair in slot order ---------------
+  // G[q*4 + t][i]: pair 4g + i of the tile, column 64q + 4(lane & 15) + t
+  float* Gs = (float*)smem;          // [16][D]
+  float* Ts = Gs + 16 * D;           // [8][16]
+  float* Cs = Ts + 8 * 16;           // [8][16]
+  for (int w = 0; w < 4; ++w) {
+    __syncthreads();  // (the first: everyone is done reading Fs)
+    if (wave == w) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        if (64 * q + 4 * l15 < D) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            f32x4* dst = (f32x4*)(Gs + (4 * g + i) * D + 64 * q + 4 * l15);
+            f32x4 v = {G[q * 4][i], G[q * 4 + 1][i], G[q * 4 + 2][i], G[q * 4 + 3][i]};
+            if (w) v = *dst + v;
+            *dst = v;
+          }
+        }
+      }
+      if (is_value) { Ts[(wave * 2 + hi) * 16 + l15] = T; Cs[(wave * 2 + hi) * 16 + l15] = C; }
+    }
+  }
+  __syncthreads();
+  {
+    float* out = p.part_g + ((size_t)split * p.Ppad + ptile * 16) * D;
+    for (int q = tid; q < 16 * D / 4; q += 256) ((f32x4*)out)[q] = ((const f32x4*)Gs)[q];
+    if (tid < 16) {
+      float t = 0.f;
+      float c = 0.f;
+      for (int slot = 0; slot < 8; ++slot) { t += Ts[slot * 16 + tid]; c += Cs[slot * 16 + tid]; }
+      p.part_t[(size_t)split * p.Ppad + ptile * 16 + tid] = t;
+      p.part_c[(size_t)split * p.Ppad + ptile * 16 + tid] = c;
+    }
+  }
+}
+
+// One block per pair: thread i adds columns 4i..4i+3 of the splits' partial gradients in split order, thread 0 the partial T and C as well.
+__global__ __launch_bounds__(64) void grad_merge_kernel(const GradP p, float* __restrict__ out) {
+  const int pair = blockIdx.x, i = threadIdx.x;
+  if (4 * i < p.D) {
+    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < p.nsplits; ++s) a += *(const f32x4*)(p.part_g + ((size_t)s * p.Ppad + pair) * p.D + 4 * i);
+    *(f32x4*)(out + (size_t)pair * p.D + 4 * i) = a;
+  }
+  if (i == 0) {
+    float t = 0.f;
+    float c = 0.f;
+    for (int s = 0; s < p.nsplits; ++s) { t += p.part_t[(size_t)s * p.Ppad + pair]; c += p.part_c[(size_t)s * p.Ppad + pair]; }
+    out[(size_t)p.P * p.D + pair] = t;
+    out[(size_t)p.P * p.D + p.P + pair] = c;
+  }
+}
+
 // Dense variant for the BLIP retrieval backend (--encoder_version blip needs the k_test = 128 best texts per frame,
 // too many for per-lane register lists): the same exact-f32 score of every (frame, text row), written out.
 __global__ __launch_bounds__(256) void scores_kernel(const float* __restrict__ img, const float* __restrict__ txt, int NF, int D,
@@ -390,9 +575,56 @@ int total_chunks(int ncat, const int32_t* seg_len, int* prefix) {
   return n;
 }
 
+// The gradient form behind vidil_scan_topk (pointers, NF, D and ncat were checked there).
+int scan_grad(const float* img, const float* txt, int NF, int D, int ncat, const int32_t* seg_start_host,
+              const int32_t* seg_len_host, void* partial, float* out, hipStream_t s) {
+  VIDIL_REQUIRE(NF % 2 == 0,
+                "scan_topk: the gradient form needs an even NF, NF/2 value rows then NF/2 weight rows (NF=%d)", NF);
+  VIDIL_REQUIRE(D <= GRAD_DMAX, "scan_topk: the gradient form keeps 16 x D accumulators in registers and needs D <= %d (D=%d)",
+                GRAD_DMAX, D);
+  VIDIL_REQUIRE((uintptr_t)partial % 16 == 0, "scan_topk: the gradient form needs a 16-byte aligned workspace");
+  VIDIL_REQUIRE((uintptr_t)out % 16 == 0, "scan_topk: the gradient form needs a 16-byte aligned out_score");
+  GradP p;
+  p.rows = img; p.keys = txt; p.P = NF / 2; p.D = D; p.ncat = ncat;
+  p.consts = img + (size_t)NF * D;
+  p.Ppad = (p.P + 15) / 16 * 16;
+  for (int c = 0; c < MAXCAT; ++c) { p.seg_start[c] = 0; p.seg_len[c] = 0; }
+  int n = 0;
+  for (int c = 0; c < ncat; ++c) {
+    VIDIL_REQUIRE(seg_len_host[c] > 0 && seg_start_host[c] >= 0 && seg_start_host[c] % 32 == 0,
+                  "scan_topk: category %d: start=%d (must be a multiple of 32) len=%d", c, seg_start_host[c], seg_len_host[c]);
+    p.seg_start[c] = seg_start_host[c];
+    p.seg_len[c] = seg_len_host[c];
+    p.split_prefix[c] = n;
+    n += ((seg_len_host[c] + 31) / 32 + GT - 1) / GT;
+  }
+  for (int c = ncat; c <= MAXCAT; ++c) p.split_prefix[c] = n;
+  p.nsplits = n;
+  p.part_g = (float*)partial;
+  p.part_t = p.part_g + (size_t)n * p.Ppad * D;
+  p.part_c = p.part_t + (size_t)n * p.Ppad;
+  const int ptiles = p.Ppad / 16;
+  VIDIL_REQUIRE(ptiles <= 65535, "scan_topk: too many pairs in one call (%d)", p.P);
+  int smem = 32 * (D + 4) * 4;
+  if (smem < (16 * D + 2 * 8 * 16) * 4) smem = (16 * D + 2 * 8 * 16) * 4;
+  const int nq = (D + 63) / 64;
+  auto kern = nq == 1 ? grad_kernel<1> : nq == 2 ? grad_kernel<2> : nq == 3 ? grad_kernel<3> : grad_kernel<4>;
+  hipLaunchKernelGGL(kern, dim3(n, ptiles), dim3(256), smem, s, p);
+  VIDIL_CHECK_LAUNCH("scan_topk/grad");
+  hipLaunchKernelGGL(grad_merge_kernel, dim3(p.P), dim3(64), 0, s, p, out);
+  VIDIL_CHECK_LAUNCH("scan_topk/grad-merge");
+  return VIDIL_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t vidil_scan_topk_ws_bytes(int32_t NF, int32_t NCpad, int32_t topk) {
+  if (NF > 0 && NCpad > 0 && topk == VIDIL_SCAN_FORM_GRAD) {
+    // one partial gradient row of 256 floats, one partial T and one partial C per (key split, pair padded to 16)
+    const int64_t splits = (int64_t)NCpad / (GT * 32) + MAXCAT + 1;
+    const int64_t ppad = ((int64_t)(NF + 1) / 2 + 15) / 16 * 16;
+    return splits * ppad * (GRAD_DMAX + 2) * 4;
+  }
   if (NF <= 0 || NCpad <= 0 || topk < 0) return 0;
   // upper bound on chunks: one per CT*32 classes plus one ragged chunk per category
   const int64_t chunks = (int64_t)NCpad / (CT * 32) + MAXCAT + 1;
@@ -407,6 +639,8 @@ extern "C" int vidil_scan_topk(const float* img, const float* txt, int32_t NF, i
   VIDIL_REQUIRE(img && txt && seg_start_host && seg_len_host && partial && out_index && out_score, "scan_topk: null pointer");
   VIDIL_REQUIRE(NF > 0 && D >= 8 && D % 8 == 0 && D <= 1024, "scan_topk: NF=%d D=%d (D%%8==0, D<=1024)", NF, D);
   VIDIL_REQUIRE(ncat >= 1 && ncat <= MAXCAT, "scan_topk: ncat=%d (1..%d)", ncat, MAXCAT);
+  if (topk == VIDIL_SCAN_FORM_GRAD)
+    return scan_grad(img, txt, NF, D, ncat, seg_start_host, seg_len_host, partial, out_score, (hipStream_t)stream);
   VIDIL_REQUIRE(topk >= 0 && topk <= TOPK_MAX, "scan_topk: topk=%d (1..%d)", topk, TOPK_MAX);
   VIDIL_REQUIRE(topk != 0 || NF % 2 == 0,
                 "scan_topk: topk == 0 (paired softmax statistics) needs an even NF, NF/2 value rows then NF/2 weight rows (NF=%d)", NF);

@@ -19,6 +19,7 @@ __all__ = [
     "gemm", "layernorm", "attention", "patchify_f32", "patchify_u8", "set_cls_row",
     "embed_tokens", "gather_rows", "l2_normalize_rows", "logsoftmax_topk", "token_logprobs", "BeamBuffers",
     "beam_update", "beam_finalize", "MAX_BEAMS", "scan_topk", "scan_topk_ws_bytes", "scan_softmax_stats",
+    "scan_softmax_grad", "SCAN_FORM_GRAD",
     "ACT_NONE", "ACT_GELU_ERF", "ACT_QUICK_GELU", "VidilHipError",
 ]
 
@@ -710,3 +711,58 @@ def scan_softmax_stats(values, weights, keys, seg_start, seg_len, workspace=None
                                       _ptr(keys, torch.float32, "scan_softmax_stats.keys"), 2 * P, D, ncat, ss, sl, 0,
                                       _ptr(workspace), _ptr(out_i), _ptr(out_s), _stream()), "scan_softmax_stats")
     return out_s, out_i
+
+
+SCAN_FORM_GRAD = -2      # VIDIL_SCAN_FORM_GRAD (include/vidil_hip.h): the value of ``topk`` that selects the gradient form
+SCAN_GRAD_MAX_D = 256
+
+
+def scan_softmax_grad(values, weights, keys, seg_start, seg_len, lse_v, lse_w, coef_v, coef_w, workspace=None, hard=None):
+    """The gradient form of the scan (vidil_scan_topk with topk == VIDIL_SCAN_FORM_GRAD), the mirror of ``scan_softmax_stats``.
+    values / weights f32 [P,D] (already divided by the temperature), D <= 256; keys f32 [NCpad,D]; seg_start/seg_len: python
+    lists per segment; lse_v, lse_w, coef_v, coef_w f32 [P].  With v_j = values[p]·keys[j] and w_j = weights[p]·keys[j] over the
+    classes j of ALL segments together and c_j = coef_v[p]·exp(v_j - lse_v[p]) - coef_w[p]·exp(w_j - lse_w[p]):
+    -> (G f32 [P,D] = sum_j c_j keys[j],  T f32 [P] = sum_j exp(v_j - lse_v[p]) v_j).  No [P,NC] matrix is written.
+    hard (i32 [P], optional): per pair a class of the FIRST segment (or -1) that is left out of G; the call then returns a third
+    tensor C f32 [P] = sum_{j != hard[p]} c_j, so that G - C[:,None] * keys[seg_start[0] + hard] = sum_{j != hard} c_j (keys[j] -
+    keys[hard]) is formed without the dominant term.  T always runs over all classes."""
+    if values.dim() != 2 or values.shape != weights.shape:
+        raise VidilHipError(f"scan_softmax_grad: values and weights must both be [P,D], got {tuple(values.shape)} and "
+                            f"{tuple(weights.shape)}")
+    P, D = values.shape
+    if D > SCAN_GRAD_MAX_D:
+        raise VidilHipError(f"scan_softmax_grad: D={D} exceeds the {SCAN_GRAD_MAX_D} columns the gradient form accumulates in registers")
+    if keys.dim() != 2 or keys.shape[1] != D:
+        raise VidilHipError(f"scan_softmax_grad: keys must be [NCpad,{D}], got {tuple(keys.shape)}")
+    if len(seg_start) != len(seg_len):
+        raise VidilHipError(f"scan_softmax_grad: {len(seg_start)} segment starts for {len(seg_len)} lengths")
+    for c, (s0, n) in enumerate(zip(seg_start, seg_len)):
+        if s0 < 0 or n <= 0 or s0 + n > keys.shape[0]:
+            raise VidilHipError(f"scan_softmax_grad: segment {c}: rows {s0}..{s0 + n} outside the {keys.shape[0]} key rows")
+    consts = (lse_v, lse_w, coef_v, coef_w)
+    for name, t in zip(("lse_v", "lse_w", "coef_v", "coef_w"), consts):
+        if tuple(t.shape) != (P,) or t.dtype != torch.float32 or t.device != values.device:
+            raise VidilHipError(f"scan_softmax_grad: {name} must be f32 [{P}] on {values.device}, got {t.dtype} "
+                                f"{tuple(t.shape)} on {t.device}")
+    ncat = len(seg_start)
+    dev = values.device
+    if hard is None:
+        hard_bits = torch.full((P,), -1, dtype=torch.int32, device=dev).view(torch.float32)
+    else:
+        if tuple(hard.shape) != (P,) or hard.dtype != torch.int32 or hard.device != dev:
+            raise VidilHipError(f"scan_softmax_grad: hard must be i32 [{P}] on {dev}, got {hard.dtype} {tuple(hard.shape)} on "
+                                f"{hard.device}")
+        hard_bits = hard.contiguous().view(torch.float32)
+    packed = torch.cat([values.reshape(-1), weights.reshape(-1), *consts, hard_bits])   # _ptr refuses host tensors, other dtypes
+    need = scan_topk_ws_bytes(2 * P, keys.shape[0], SCAN_FORM_GRAD)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    out = torch.empty((P * D + 2 * P,), dtype=torch.float32, device=dev)
+    unused = torch.empty((1,), dtype=torch.int32, device=dev)               # out_index: non-null, not written
+    ss = (C.c_int32 * ncat)(*seg_start)
+    sl = (C.c_int32 * ncat)(*seg_len)
+    check(_lib.load().vidil_scan_topk(_ptr(packed, torch.float32, "scan_softmax_grad.rows"),
+                                      _ptr(keys, torch.float32, "scan_softmax_grad.keys"), 2 * P, D, ncat, ss, sl,
+                                      SCAN_FORM_GRAD, _ptr(workspace), _ptr(unused), _ptr(out), _stream()), "scan_softmax_grad")
+    G, T, Csum = out[:P * D].view(P, D), out[P * D:P * D + P], out[P * D + P:]
+    return (G, T) if hard is None else (G, T, Csum)
