@@ -184,7 +184,19 @@ typedef struct vidil_gemm_args {
  * allocations.  The padding columns of A (lda > K) may hold anything, NaNs included (observed by the test).  So may the memory
  * behind the last rows of A and W, as far as a staging load reaches it at all: row m of A feeds row m of the product only, row n
  * of W column n only, and rows >= M / columns >= N are never stored (this follows from the masking; the test keeps one tile of
- * NaN rows there).  With operands whose products and sums are exact in f32 the result is exact, whichever form serves the call. */
+ * NaN rows there).  With operands whose products and sums are exact in f32 the result is exact, whichever form serves the call.
+ *
+ * Pinned by tests/test_gemm_stat_forms_gpu.py (ln_fold, out16 / ln_stats_out, rln, out16_split3, fp8 operands; both 256-row kernels,
+ * which agree bit for bit, and the compensated form as a producer of planes):
+ *   ln_stats is used AS GIVEN: mean and rstd of row m come from the partials of row m alone, all K / 64 (rln: N / 64) of them, each
+ *     counted once — the kernels never recompute them from A — so with partials, eps and vectors that make the chain exact in f32
+ *     the fold and the residual LayerNorm are exact too;
+ *   ln_stats_out: pairs of rows >= M are not written; out16 rows >= M and columns N .. ldo16 - 1 are not written, and
+ *     out16 == T16(out) bit for bit;
+ *   out16_split3: plane 0 == T16(v), plane 1 == T16(v - plane 0), plane 2 == plane 0 (1) or UNTOUCHED (2); the columns
+ *     N .. ldo16 / 3 - 1 of every plane are untouched; with out == NULL no f32 row is written and the planes are the same bits;
+ *   fp8: w_scale[n] and bias[n] apply to column n; EPI_F8 rounds to nearest even and SATURATES at +-448 (never NaN from a finite
+ *     value); EPI_F32 applies `act` (on the 8-wave kernel, the only one built for it). */
 int vidil_gemm(const vidil_gemm_args* args, void* stream);
 /* (ABI 12) Per CALL: 1 when vidil_gemm would run `args` (split_k != 0) in the K-loop form — planes 0 / 1 of the A rows are
  * all it reads, so their producer may be run with VIDIL_DT_SPLIT2 / out16_split3 = 2 / out_mode 3 —, 0 when it would run the plain

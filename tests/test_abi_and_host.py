@@ -145,6 +145,40 @@ def test_argument_validation_without_a_gpu():
     assert lib.vidil_gemm_kernel_name(ctypes.byref(g), buf, 128) == -1 and b"w_scale" in lib.vidil_last_error()
     g.w_scale = 16
     assert lib.vidil_gemm_kernel_name(ctypes.byref(g), buf, 128) == 0 and buf.value == b"gemm256_kernel<fp8, _Float16, 1, 0, false, false, false>"
+    # the refusals of the epilogue features (ln_fold, out16, out16_split3, ln_stats_out, rln, fp8, split_k): each from a struct that
+    # is valid but for the one field named (tests/test_gemm_stat_forms_gpu.py covers what is inside the contract)
+    def gemm_refused(needle, base, **fields):
+        plain = dict(A=16, W=16, out=16, M=300, N=128, K=256, ldo=128, epi=0, dtype=0)
+        a, ok = _lib.GemmArgs(), _lib.GemmArgs()
+        for k, v in {**plain, **base, **fields}.items():
+            setattr(a, k, v)
+        for k, v in {**plain, **base}.items():
+            setattr(ok, k, v)
+        assert lib.vidil_gemm_kernel_name(ctypes.byref(ok), buf, 128) == 0, (needle, lib.vidil_last_error())
+        assert lib.vidil_gemm(ctypes.byref(a), None) == -1 and needle in lib.vidil_last_error(), (needle, lib.vidil_last_error())
+
+    fold = dict(ln_fold=1, ln_colsum=16, ln_stats=16, ln_eps=1e-5)
+    gemm_refused(b"A rows must be dense", fold, lda=264)
+    gemm_refused(b"LayerNorm widths up to 1024", fold, K=1088)
+    gemm_refused(b"only EPI_F16 / EPI_HEADS / EPI_ARENA consume", fold, epi=1)
+    gemm_refused(b"gemm/split_k", dict(K=192, **fold), split_k=1)
+    prod = dict(epi=1, out16=16, ldo16=128)
+    gemm_refused(b"only the f32 residual epilogue writes the 16-bit copy", prod, epi=0)
+    split3 = dict(epi=1, out16=16, ldo16=384, out16_split3=1)
+    gemm_refused(b"three planes", split3, ldo16=388)
+    gemm_refused(b"gemm/out16_split3: the plain f32 epilogue", split3, ln_stats_out=16)
+    stats = dict(prod, ln_stats_out=16)
+    gemm_refused(b"gemm/ln_stats_out", stats, N=136, ldo=136, ldo16=136)
+    gemm_refused(b"gemm/ln_stats_out", stats, act=1)
+    rln = dict(stats, resid=16, rln_gamma=16, rln_beta=16, ln_stats=16, ln_eps=1e-5)
+    gemm_refused(b"gemm/rln: the residual LayerNorm needs", rln, ln_stats_out=None)
+    gemm_refused(b"dense residual rows", rln, ldo=136)
+    gemm_refused(b"dense residual rows", rln, N=1088, ldo=1088, ldo16=1088)
+    fp8 = dict(dtype=2, dtype16=0, w_scale=16, epi=1)
+    gemm_refused(b"is not built for fp8 operands", fp8, epi=0)
+    gemm_refused(b"w_scale", fp8, w_scale=None)
+    gemm_refused(b"multiple of 128", fp8, K=192)
+    gemm_refused(b"EPI_F8 needs fp8 operands", dict(), epi=5)
     # out_dtype of the attention: fp8 only from the staged kernel
     assert lib.vidil_attention(16, 16, 16, 16, None, None, None, 0, 0, 1, 12, 4, 64, 4, 64, 64, 1, 0, 0, 768, 0, 0, 2, None) == -1
     assert b"out_dtype" in lib.vidil_last_error()

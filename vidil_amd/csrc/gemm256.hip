@@ -445,7 +445,12 @@ static int launch256_dispatch(const vidil_gemm_args& a, hipStream_t s) {
 template <typename TO>
 static int launch256_fp8(const vidil_gemm_args& a, hipStream_t s) {
   switch (a.epi) {
-    case VIDIL_EPI_F32: return launch256<fp8, VIDIL_EPI_F32, VIDIL_ACT_NONE, false, TO>(a, s);
+    case VIDIL_EPI_F32:
+      // (the activation is part of the call — check_args admits it and vidil_gemm_kernel_name prints it; the 4-wave kernel
+      //  answers -1000 for it, so this is the one body that serves it)
+      if (a.act == VIDIL_ACT_GELU_ERF) return launch256<fp8, VIDIL_EPI_F32, VIDIL_ACT_GELU_ERF, false, TO>(a, s);
+      if (a.act == VIDIL_ACT_QUICK_GELU) return launch256<fp8, VIDIL_EPI_F32, VIDIL_ACT_QUICK_GELU, false, TO>(a, s);
+      return launch256<fp8, VIDIL_EPI_F32, VIDIL_ACT_NONE, false, TO>(a, s);
     case VIDIL_EPI_PATCH: return launch256<fp8, VIDIL_EPI_PATCH, VIDIL_ACT_NONE, false, TO>(a, s);
     case VIDIL_EPI_HEADS: return launch256<fp8, VIDIL_EPI_HEADS, VIDIL_ACT_NONE, false, TO>(a, s);
     case VIDIL_EPI_F8:
@@ -498,7 +503,12 @@ static bool prefer_4w(const vidil_gemm_args& a) {
   }
 }
 
-const char* vidil_gemm256_variant(const vidil_gemm_args& a) { return prefer_4w(a) ? "gemm4w_kernel" : "gemm256_kernel"; }
+// (fp8 operands with an activation on f32 rows or with the patch epilogue: launch4w_fp8 answers -1000 — the launch below falls back
+//  to the 8-wave kernel whatever $VIDIL_GEMM4W says, and the name has to say so too)
+static bool built_4w(const vidil_gemm_args& a) {
+  return !(a.dtype == VIDIL_DT_FP8 && (a.epi == VIDIL_EPI_PATCH || (a.epi == VIDIL_EPI_F32 && a.act != VIDIL_ACT_NONE)));
+}
+const char* vidil_gemm256_variant(const vidil_gemm_args& a) { return prefer_4w(a) && built_4w(a) ? "gemm4w_kernel" : "gemm256_kernel"; }
 
 // The 128 x 256-tile form of gemm4w for problems with too few 256 x 256 tiles to fill the chip but about one 128 x 256
 // tile per CU or more (the decode steps' projections and FFN at ~10^4 beam rows): 16-bit operands, plain epilogues.
