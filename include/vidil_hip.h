@@ -68,7 +68,11 @@ enum {
   VIDIL_EPI_HEADS = 2, /* scatter into per-head Q / K / V^T buffers (see below)            */
   VIDIL_EPI_PATCH = 3, /* out f32 row (m + m/tpi + 1) = acc + bias + pos[(m%tpi)+1]        */
   VIDIL_EPI_ARENA = 4, /* Q rows + K / V rows appended to a beam-search KV arena (below)   */
-  VIDIL_EPI_F8 = 5     /* out fp8 (e4m3) [M,ldo] = act(acc * w_scale + bias): the fc1 -> fc2 hand-over of the fp8 mode */
+  VIDIL_EPI_F8 = 5,    /* out fp8 (e4m3) [M,ldo] = act(acc * w_scale + bias): the fc1 -> fc2 hand-over of the fp8 mode */
+  /* The two BACKWARD forms of a Linear y = x · W^T (no ABI bump: two further values of `epi`, refused as unsupported by older
+   * libraries).  Other operand layouts than the product above — see "Backward forms" below the struct. */
+  VIDIL_EPI_GRAD_IN = 6, /* out f32 [M,ldo] = A[M,K] · W[K,N] (+ resid):   dX = dY · W, W as the forward's [Nout,Kin] weight  */
+  VIDIL_EPI_GRAD_W = 7   /* out f32 [N,ldo] = A[M,N]^T · W[M,K] (+ resid): dW = dY^T · X, the contraction runs over the rows  */
 };
 enum { VIDIL_ACT_NONE = 0, VIDIL_ACT_GELU_ERF = 1, VIDIL_ACT_QUICK_GELU = 2 };
 
@@ -196,7 +200,36 @@ typedef struct vidil_gemm_args {
  *   out16_split3: plane 0 == T16(v), plane 1 == T16(v - plane 0), plane 2 == plane 0 (1) or UNTOUCHED (2); the columns
  *     N .. ldo16 / 3 - 1 of every plane are untouched; with out == NULL no f32 row is written and the planes are the same bits;
  *   fp8: w_scale[n] and bias[n] apply to column n; EPI_F8 rounds to nearest even and SATURATES at +-448 (never NaN from a finite
- *     value); EPI_F32 applies `act` (on the 8-wave kernel, the only one built for it). */
+ *     value); EPI_F32 applies `act` (on the 8-wave kernel, the only one built for it).
+ *
+ * Backward forms (VIDIL_EPI_GRAD_IN / VIDIL_EPI_GRAD_W; 16-bit operands `dtype`, f32 accumulation and output):
+ *   GRAD_IN: out[m][n] = sum_{k<K} A[m][k] · W[k][n] (+ resid[m][n]).  A T16 [M,K], row stride lda (0 = K; >= K, % 8 == 0);
+ *            W T16 dense [K,N], N % 8 == 0; out f32 [M,ldo], ldo >= N; the contraction length K % 8 == 0 (NOT % 64).
+ *   GRAD_W:  out[n][k] = sum_{m<M} A[m][n] · W[m][k] (+ resid[n][k]).  A T16 [M,N], row stride lda (0 = N, then N % 8 == 0;
+ *            >= N, % 8 == 0); W T16 dense [M,K], K % 8 == 0; out f32 [N,ldo], ldo >= K; the contraction length is M, any M >= 1.
+ *   resid: f32 with the shape and ldo of out, or NULL; it may alias out (gradient accumulation).  A, W and out 16-byte aligned.
+ *   Refused with VIDIL_EINVAL: bias, act, ln_fold, out16, out16_split3, ln_stats_out, rln_*, split_k, VIDIL_DT_FP8.
+ *   Workspace: a contraction that is long against the number of output tiles is split over workgroups; the partial products
+ *   then go to an f32 workspace the caller passes in `q` (a field these forms do not otherwise use; 16-byte aligned) and a
+ *   merge step adds them in split order (no atomics).  With R x C the output (GRAD_IN: M x N, GRAD_W: N x K) and L the
+ *   contraction length (K / M):
+ *       bt     = 128 if ceil(R/128) * ceil(C/128) >= 64 else 64                     (the output tile is bt x bt)
+ *       ns     = max(1, min(ceil(L/128), 512 / (ceil(R/bt) * ceil(C/bt)), 16))      (integer division)
+ *       len    = 64 * ceil(ceil(L/ns) / 64),  nsplit = ceil(L/len)                  (split i covers rows i*len .. of the contraction)
+ *       bytes  = nsplit > 1 ? 4 * nsplit * R * C : 0                                (`q` may be NULL when 0)
+ *   — a function of (M, N, K) alone, never of the device or an environment switch (VIDIL_GEMM256 / VIDIL_GEMM4W do not reach
+ *   these forms).  vidil_amd.kernels.gemm_grad_ws_bytes restates it.  vidil_gemm_split_k_serves answers 0 for these calls.
+ *
+ * Pinned by tests/test_gemm_grad_gpu.py (both forms, f16 and bf16, both tiles, split and unsplit):
+ *   a launch writes out[r][c] for r < R, c < C and NOTHING else — not the columns C .. ldo - 1, not a row >= R, not a neighbouring
+ *     allocation, and nothing behind the workspace's `bytes`;
+ *   elements past the contraction edge contribute EXACTLY zero whatever the memory holds, NaNs included, because they are not
+ *     read: GRAD_W never dereferences a row >= M of A or W (they may be unmapped), GRAD_IN never a row >= K of W, and the
+ *     columns K .. lda - 1 of a GRAD_IN A row are never read either;
+ *   GRAD_W: element (n, k) depends only on column n of A and column k of W; the columns N .. lda - 1 of A (read as far as the
+ *     8-column chunk that holds column N - 1 reaches) feed only outputs that are never stored, so they may hold NaNs;
+ *   with operands whose products and partial sums are exact in f32 the result is exact, whichever tile / split serves the call;
+ *   the same arguments give the same bits on every call, and inside any ldo. */
 int vidil_gemm(const vidil_gemm_args* args, void* stream);
 /* (ABI 12) Per CALL: 1 when vidil_gemm would run `args` (split_k != 0) in the K-loop form — planes 0 / 1 of the A rows are
  * all it reads, so their producer may be run with VIDIL_DT_SPLIT2 / out16_split3 = 2 / out_mode 3 —, 0 when it would run the plain

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIDIL_HIP_LIB") or os.path.join(_HERE, "csrc", "libvidil_hip.so")
 
 EPI_F16, EPI_F32, EPI_HEADS, EPI_PATCH, EPI_ARENA, EPI_F8 = 0, 1, 2, 3, 4, 5
+EPI_GRAD_IN, EPI_GRAD_W = 6, 7     # the backward forms dX = dY · W and dW = dY^T · X (include/vidil_hip.h "Backward forms")
 DT_F16, DT_BF16, DT_FP8 = 0, 1, 2
 DT_SPLIT3 = 0x100     # output flag: rows written as error-compensated operands [hi | lo | hi] (include/vidil_hip.h)
 DT_SPLIT2 = 0x200      # with DT_SPLIT3: planes hi | lo written only (include/vidil_hip.h VIDIL_DT_SPLIT2)

@@ -80,10 +80,13 @@ class BLIP_ITM(PackedCache, nn.Module):
             return self._project_cls_parity(y32, n_images, y32.numel() // (n_images * y32.shape[-1]), p["vp_w3"], p["vp_b"])
         return self._project_cls(y16, n_images, y16.shape[0] // n_images, p["vp_w"], p["vp_b"])
 
-    def text_embeds(self, d_ids, d_lens):
-        """Unit-norm ITC text embeddings of right-padded ids i32 [N, T] (device) through the text encoder in mode='text'."""
+    def text_embeds(self, d_ids, d_lens, capture=None):
+        """Unit-norm ITC text embeddings of right-padded ids i32 [N, T] (device) through the text encoder in mode='text'.
+        capture (dict): receives ``text_cls``, a copy of the 16-bit [CLS] rows [N, width] the projection read (plain mode)."""
         p = self.packed()
         h32, h16 = self.text_encoder.encode(d_ids, d_lens, None)       # mode='text': no cross-attention
+        if capture is not None:
+            capture["text_cls"] = h16.view(d_ids.shape[0], d_ids.shape[1], -1)[:, 0].contiguous()
         if p["parity"]:
             return self._project_cls_parity(h32, d_ids.shape[0], d_ids.shape[1], p["tp_w3"], p["tp_b"])
         return self._project_cls(h16, d_ids.shape[0], d_ids.shape[1], p["tp_w"], p["tp_b"])
@@ -130,7 +133,7 @@ class BLIP_ITM(PackedCache, nn.Module):
 
     @torch.no_grad()
     def itm_pairs(self, enc16, n_images, ids, lens, image_index=None, group_start=None, max_group=0, pair_text=None,
-                  cross=None, t_eff=None):
+                  cross=None, t_eff=None, capture=None):
         """enc16 f16 [n_images*Te, width]; ids i32 [P,35]; lens i32 [P].  Either image_index i32 [P] (pair ->
         image, any order) or, for IMAGE-MAJOR pair order, group_start i32 [n_images+1] (pairs of image j are
         group_start[j] .. group_start[j+1]-1, at most max_group of them), which lets one fetch of an image's
@@ -140,6 +143,7 @@ class BLIP_ITM(PackedCache, nn.Module):
         t_eff: the token count every text is cut to (default: this call's longest text) — a caller that scores one set of pairs
         in several calls passes the longest text of ALL of them, so that a pair's launches do not depend on its call.
         More than BertModel.LONG_KEYS tokens per image (a video as one image of N*T tokens) need the group_start form.
+        capture (dict): receives ``itm_cls``, the 16-bit [CLS] rows [P, width] the head read (plain mode), in this call's pair order.
         Returns f32 [P,2] raw ITM logits."""
         require_cuda(enc16, "BLIP_ITM")
         te = self.text_encoder
@@ -194,6 +198,8 @@ class BLIP_ITM(PackedCache, nn.Module):
         # only token 0 feeds the itm_head: the last layer runs on the [CLS] rows alone (BertModel.encode_cls)
         _, c16 = te.encode_cls(ids, lens, cross, cross_index=image_index, cross_groups=group_start,
                                cross_max_group=max_group, pair_text=pair_text)
+        if capture is not None:
+            capture["itm_cls"] = c16
         out = torch.empty((P, 2), dtype=torch.float32, device=dev)
         K.gemm(c16, p["itm_w"], p["itm_b"], out=out)
         return out

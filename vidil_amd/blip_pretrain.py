@@ -97,7 +97,8 @@ class BLIP_Pretrain(BLIP_Retrieval):
         return self.packed()
 
     @torch.no_grad()
-    def forward(self, image, caption, alpha, *, negatives=None, seed=None, details=None, timings=None, grads=None):
+    def forward(self, image, caption, alpha, *, negatives=None, seed=None, details=None, timings=None, grads=None,
+                head_grads=None):
         """models/blip_pretrain.py:97-212 (BLIP_Pretrain_Video: :328-452) -> (loss_ita, loss_itm, loss_lm), 0-dim
         f32 device tensors.  image f32 [B,3,S,S] (video: [B,N,3,S,S]); caption: B strings; alpha: float.
         negatives = (neg_image_of_text, neg_text_of_image), int [B] each: given draws instead of this library's own Philox draws
@@ -109,6 +110,8 @@ class BLIP_Pretrain(BLIP_Retrieval):
         grads (dict) receives ``image_feat``, ``text_feat`` (f32 [B, embed_dim]) and ``temp`` (0-dim f32): the gradients of
         ``loss_ita`` only with respect to the online features and the temperature (partial gradients of the total loss; see
         ``BLIP_Retrieval.loss_forward``).  Losses, ``details`` and every state change are the bits of the call without it.
+        head_grads (dict) receives the backward of vision_proj, text_proj (``loss_ita``) and itm_head (``loss_itm``) with the
+        keys and rules of ``BLIP_Retrieval.loss_forward``; ``loss_lm`` gets nothing.
         Order of effects as in the reference: temp clamp, online features, EMA, momentum features, ITC loss, enqueue, negatives,
         the ITM pass, the LM pass."""
         who = f"{type(self).__name__}.forward"
@@ -133,7 +136,8 @@ class BLIP_Pretrain(BLIP_Retrieval):
         ids, lens = self.tokenize(caption)                                                  # :105
         t_eff = max(1, int(lens.max().item()))
         d_ids, d_lens = ids[:, :t_eff].to(dev).contiguous(), lens.to(dev).contiguous()
-        text_feat = self.text_embeds(d_ids, d_lens)                                         # :107-109
+        captured = {} if head_grads is not None else None
+        text_feat = self.text_embeds(d_ids, d_lens, captured)                               # :107-109
         t0 = lap("text", t0)
 
         self._momentum_update()                                                             # :113
@@ -146,8 +150,12 @@ class BLIP_Pretrain(BLIP_Retrieval):
         t0 = lap("momentum", t0)
 
         # ---- image-text contrastive loss (:123-138) and the enqueue (:140)
+        if head_grads is not None and grads is None:
+            grads = {}                                                                       # (the head backward starts from them)
         loss_ita, loss_i2t, loss_t2i, sim_i2t, sim_t2i = self._itc_losses(image_feat, text_feat, image_feat_m, text_feat_m, alpha,
                                                                           temp, grads)
+        if head_grads is not None:
+            self._head_grads_itc(head_grads, grads, self._image_cls_rows(enc16, image), captured["text_cls"])
         self._dequeue_and_enqueue(image_feat_m, text_feat_m)
         t0 = lap("itc", t0)
 
@@ -158,7 +166,9 @@ class BLIP_Pretrain(BLIP_Retrieval):
             neg_text = self._draw_from_weights((torch.softmax(sim_i2t, dim=1) + 1e-4).fill_diagonal_(0), seed, 1)
         else:
             neg_image, neg_text = negatives[0].to(dev), negatives[1].to(dev)
-        vl_output, loss_itm = self._itm_loss(enc16, B, ids, lens, neg_image, neg_text)
+        vl_output, loss_itm = self._itm_loss(enc16, B, ids, lens, neg_image, neg_text, captured)
+        if head_grads is not None:
+            self._head_grads_itm(head_grads, vl_output, captured["itm_cls"])
         t0 = lap("itm", t0)
 
         # ---- language modelling on the same tokens (:199-211): every token after [DEC] is a target, the closing [SEP] included
@@ -183,8 +193,10 @@ class BLIP_Pretrain_Video(BLIP_Pretrain, BLIP_Retrieval_Video):
     # (the visual side — frame tokens, the mean-of-frames feature, the token limit — is BLIP_Retrieval_Video's, inherited)
 
     @torch.no_grad()
-    def forward(self, video, caption, alpha, *, negatives=None, seed=None, details=None, timings=None, grads=None):
-        return super().forward(video, caption, alpha, negatives=negatives, seed=seed, details=details, timings=timings, grads=grads)
+    def forward(self, video, caption, alpha, *, negatives=None, seed=None, details=None, timings=None, grads=None,
+                head_grads=None):
+        return super().forward(video, caption, alpha, negatives=negatives, seed=seed, details=details, timings=timings, grads=grads,
+                               head_grads=head_grads)
 
 
 def _from_pretrained(model, pretrained):

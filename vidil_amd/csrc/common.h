@@ -34,6 +34,10 @@ bool vidil_gemm4w128_wanted(const vidil_gemm_args& a);          // the 128 x 256
 int vidil_gemm4w128_launch(const vidil_gemm_args& a, hipStream_t s);
 bool vidil_gemm_c3_serves(const vidil_gemm_args& a);            // gemm.hip: a split_k launch that the in-loop compensated kernel takes (at every size)
 int vidil_gemm4w_c3_launch(const vidil_gemm_args& a, hipStream_t s);   // gemm4w.hip
+// gemm_grad.hip: the backward forms VIDIL_EPI_GRAD_IN / VIDIL_EPI_GRAD_W of vidil_gemm
+int vidil_gemm_grad_check(const vidil_gemm_args& a);
+int vidil_gemm_grad_launch(const vidil_gemm_args& a, hipStream_t s);
+void vidil_gemm_grad_kernel_name(const vidil_gemm_args& a, char* buf, int n);
 
 #define VIDIL_REQUIRE(cond, ...)                \
   do {                                          \

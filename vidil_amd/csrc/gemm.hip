@@ -369,6 +369,7 @@ int pick_tile(const vidil_gemm_args& a, hipStream_t s) {
 // argument checks shared by vidil_gemm and vidil_gemm_kernel_name
 int check_args(const vidil_gemm_args& a) {
   VIDIL_REQUIRE(a.A && a.W, "gemm: null operand");
+  if (a.epi == VIDIL_EPI_GRAD_IN || a.epi == VIDIL_EPI_GRAD_W) return vidil_gemm_grad_check(a);   // the backward forms: gemm_grad.hip
   VIDIL_REQUIRE(a.dtype == VIDIL_DT_F16 || a.dtype == VIDIL_DT_BF16 || a.dtype == VIDIL_DT_FP8, "gemm: unknown dtype %d", a.dtype);
   if (a.dtype == VIDIL_DT_FP8) {
     VIDIL_REQUIRE(a.K % 128 == 0, "gemm/fp8: K=%d must be a multiple of 128", a.K);
@@ -522,6 +523,7 @@ extern "C" int vidil_gemm(const vidil_gemm_args* args, void* stream) {
   VIDIL_REQUIRE(args != nullptr, "gemm: null args");
   const int rc = check_args(*args);
   if (rc != VIDIL_OK) return rc;
+  if (args->epi == VIDIL_EPI_GRAD_IN || args->epi == VIDIL_EPI_GRAD_W) return vidil_gemm_grad_launch(*args, (hipStream_t)stream);
   if (vidil_gemm_c3_serves(*args)) {
     const int rc3 = vidil_gemm4w_c3_launch(*args, (hipStream_t)stream);
     if (rc3 != -1000) return rc3;
@@ -543,6 +545,10 @@ extern "C" int vidil_gemm_kernel_name(const vidil_gemm_args* args, char* buf_hos
   VIDIL_REQUIRE(args != nullptr && buf_host != nullptr && n > 0, "gemm_kernel_name: bad args");
   const int rc = check_args(*args);
   if (rc != VIDIL_OK) return rc;
+  if (args->epi == VIDIL_EPI_GRAD_IN || args->epi == VIDIL_EPI_GRAD_W) {
+    vidil_gemm_grad_kernel_name(*args, buf_host, n);
+    return VIDIL_OK;
+  }
   const TileChoice c = choose_tile(*args);
   const char* t16 = (args->dtype == VIDIL_DT_FP8 ? args->dtype16 : args->dtype) == VIDIL_DT_BF16 ? "__bf16" : "_Float16";
   if (vidil_gemm_c3_serves(*args)) {

@@ -13,13 +13,13 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_GELU_ERF, ACT_NONE, ACT_QUICK_GELU, DT_BF16, DT_F16, DT_FP8, DT_SPLIT2, DT_SPLIT3, EPI_ARENA, EPI_F8, EPI_F16, EPI_F32,
-                   EPI_HEADS, EPI_PATCH, BeamState, GemmArgs, VidilHipError, check)
+                   EPI_GRAD_IN, EPI_GRAD_W, EPI_HEADS, EPI_PATCH, BeamState, GemmArgs, VidilHipError, check)
 
 __all__ = [
     "gemm", "layernorm", "attention", "patchify_f32", "patchify_u8", "set_cls_row",
     "embed_tokens", "gather_rows", "l2_normalize_rows", "logsoftmax_topk", "token_logprobs", "BeamBuffers",
     "beam_update", "beam_finalize", "MAX_BEAMS", "scan_topk", "scan_topk_ws_bytes", "scan_softmax_stats",
-    "scan_softmax_grad", "SCAN_FORM_GRAD",
+    "scan_softmax_grad", "SCAN_FORM_GRAD", "gemm_grad_input", "gemm_grad_weight", "gemm_grad_ws_bytes",
     "ACT_NONE", "ACT_GELU_ERF", "ACT_QUICK_GELU", "VidilHipError",
 ]
 
@@ -249,6 +249,120 @@ def _gemm_build(a, w, bias=None, *, out=None, out_dtype=None, act=ACT_NONE, resi
         g.ln_stats = _ptr(stats, torch.float32, "gemm.ln_stats")
         g.ln_eps = float(eps)
     return g, ret
+
+
+# ------------------------------------------------------------------- backward GEMM forms
+def gemm_grad_plan(form, M, N, K):
+    """(tile, nsplit, split_len) of a backward-form launch: the formula of include/vidil_hip.h "Backward forms", restated.
+    A function of the form and (M, N, K) alone."""
+    if form not in (EPI_GRAD_IN, EPI_GRAD_W):
+        raise VidilHipError(f"gemm_grad_plan: form must be EPI_GRAD_IN ({EPI_GRAD_IN}) or EPI_GRAD_W ({EPI_GRAD_W}), got {form}")
+    R, Cc, L = (M, N, K) if form == EPI_GRAD_IN else (N, K, M)
+    cdiv = lambda a, b: -(-a // b)
+    bt = 128 if cdiv(R, 128) * cdiv(Cc, 128) >= 64 else 64
+    ns = max(1, min(cdiv(L, 128), 512 // (cdiv(R, bt) * cdiv(Cc, bt)), 16))
+    split_len = 64 * cdiv(cdiv(L, ns), 64)
+    return bt, cdiv(L, split_len), split_len
+
+
+def gemm_grad_ws_bytes(form, M, N, K):
+    """Bytes of the f32 workspace a backward-form launch needs for its partial products (0: the contraction is not split)."""
+    _, nsplit, _ = gemm_grad_plan(form, M, N, K)
+    R, Cc = (M, N) if form == EPI_GRAD_IN else (N, K)
+    return 4 * nsplit * R * Cc if nsplit > 1 else 0
+
+
+def _gemm_grad_build(form, a, w, out, resid, M, lda, workspace):
+    who = "gemm_grad_input" if form == EPI_GRAD_IN else "gemm_grad_weight"
+    if a.dim() != 2 or w.dim() != 2:
+        raise VidilHipError(f"{who}: operands must be 2-D, got {tuple(a.shape)} and {tuple(w.shape)}")
+    if w.dtype != a.dtype:
+        raise VidilHipError(f"{who}: operands must share one 16-bit type, got {a.dtype} and {w.dtype}")
+    dt = _dt(a, f"{who}.dy")
+    if lda is None:
+        if M is not None and M != a.shape[0]:
+            raise VidilHipError(f"{who}: M={M} but dy has {a.shape[0]} rows (a strided dy needs lda)")
+        M, cols = a.shape
+        lda_arg = 0
+    else:
+        if M is None:
+            raise VidilHipError(f"{who}: strided dy (lda) needs an explicit M")
+        if M < 1 or lda < 1:
+            raise VidilHipError(f"{who}: M={M} and lda={lda} must be positive")
+        if form == EPI_GRAD_W and (out is None or out.dim() != 2):
+            raise VidilHipError(f"{who}: a strided dy (lda) needs a 2-D `out` [Nout, >= Kin] to name Nout")
+        # what the kernel reads of the last row: GRAD_IN its K = w.shape[0] columns, GRAD_W up to the 8-column chunk that holds
+        # column Nout - 1
+        last = w.shape[0] if form == EPI_GRAD_IN else (out.shape[0] + 7) // 8 * 8
+        if a.numel() < (M - 1) * lda + last:
+            raise VidilHipError(f"{who}: dy holds {a.numel()} elements, fewer than the {(M - 1) * lda + last} that M={M} rows of "
+                                f"stride {lda} reach")
+        cols, lda_arg = None, lda
+    if form == EPI_GRAD_IN:                    # dy [M, Nout] · w [Nout, Kin]: the contraction is the library's K
+        Kc, Nn = w.shape
+        if cols is not None and cols != Kc:
+            raise VidilHipError(f"{who}: dy is {tuple(a.shape)} but w is {tuple(w.shape)} (dy columns = w rows)")
+        R, Cc = M, Nn
+        if Kc % 8 or Nn % 8:
+            raise VidilHipError(f"{who}: w {tuple(w.shape)}: both dimensions must be multiples of 8")
+        if lda is not None and (lda < Kc or lda % 8):
+            raise VidilHipError(f"{who}: lda={lda} must be >= {Kc} and a multiple of 8")
+    else:                                      # dy [M, Nout]^T · x [M, Kin]: the contraction is the library's M
+        Mx, Kc = w.shape
+        if Mx != M:
+            raise VidilHipError(f"{who}: dy has M={M} rows but x is {tuple(w.shape)}")
+        if lda is None:
+            Nn = cols
+            if Nn % 8:
+                raise VidilHipError(f"{who}: a dense dy needs Nout={Nn} to be a multiple of 8 (pass lda and Nout through out)")
+        else:
+            Nn = out.shape[0]
+            if lda < Nn or lda % 8:
+                raise VidilHipError(f"{who}: lda={lda} must be >= Nout={Nn} and a multiple of 8")
+        if Kc % 8:
+            raise VidilHipError(f"{who}: x {tuple(w.shape)}: Kin must be a multiple of 8")
+        R, Cc = Nn, Kc
+    if out is None:
+        out = torch.empty((R, Cc), dtype=torch.float32, device=a.device)
+    if out.dim() != 2 or out.shape[0] != R or out.shape[1] < Cc or out.dtype != torch.float32:
+        raise VidilHipError(f"{who}: out must be f32 [{R}, >= {Cc}], got {out.dtype} {tuple(out.shape)}")
+    if resid is not None and (resid.dtype != torch.float32 or tuple(resid.shape) != tuple(out.shape)):
+        raise VidilHipError(f"{who}: resid must be f32 {tuple(out.shape)} like out, got {resid.dtype} {tuple(resid.shape)}")
+    g = GemmArgs()
+    g.dtype = dt
+    g.A, g.W = _ptr(a, a.dtype, f"{who}.dy"), _ptr(w, a.dtype, f"{who}.w")
+    g.M, g.N, g.K = (M, Nn, Kc)
+    g.lda = lda_arg
+    g.epi, g.act = form, ACT_NONE
+    g.out, g.ldo = _ptr(out, torch.float32, f"{who}.out"), out.shape[1]
+    g.resid = _ptr(resid, torch.float32, f"{who}.resid")
+    need = gemm_grad_ws_bytes(form, M, Nn, Kc)
+    if need:
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=a.device)
+        elif workspace.numel() * workspace.element_size() < need:
+            raise VidilHipError(f"{who}: workspace holds {workspace.numel() * workspace.element_size()} bytes, {need} needed "
+                                f"(gemm_grad_ws_bytes)")
+        g.q = _ptr(workspace, None, f"{who}.workspace")
+    return g, out, workspace
+
+
+def gemm_grad_input(dy16, w16, *, out=None, resid=None, M=None, lda=None, workspace=None):
+    """dX = dY · W (VIDIL_EPI_GRAD_IN): dy16 T16 [M, Nout] (row stride ``lda`` with an explicit ``M``), w16 T16 [Nout, Kin] exactly as
+    the forward's weight is stored; returns/fills f32 ``out`` [M, >= Kin] (+ ``resid``, which may be ``out``).  Nout and Kin
+    multiples of 8.  ``workspace``: >= ``gemm_grad_ws_bytes(EPI_GRAD_IN, M, Kin, Nout)`` bytes, allocated when None."""
+    g, out, ws = _gemm_grad_build(EPI_GRAD_IN, dy16, w16, out, resid, M, lda, workspace)
+    check(_lib.load().vidil_gemm(C.byref(g), _stream()), "gemm_grad_input")
+    return out
+
+
+def gemm_grad_weight(dy16, x16, *, out=None, resid=None, M=None, lda=None, workspace=None):
+    """dW = dY^T · X (VIDIL_EPI_GRAD_W): dy16 T16 [M, Nout] (row stride ``lda`` with explicit ``M`` and ``out``), x16 T16 [M, Kin];
+    returns/fills f32 ``out`` [Nout, >= Kin] (+ ``resid``, which may be ``out``: gradient accumulation).  Kin a multiple of 8, any M.
+    ``workspace``: >= ``gemm_grad_ws_bytes(EPI_GRAD_W, M, Nout, Kin)`` bytes, allocated when None."""
+    g, out, ws = _gemm_grad_build(EPI_GRAD_W, dy16, x16, out, resid, M, lda, workspace)
+    check(_lib.load().vidil_gemm(C.byref(g), _stream()), "gemm_grad_weight")
+    return out
 
 
 # ---------------------------------------------------------------------- row kernels

@@ -21,8 +21,12 @@ either); dL_b/dq = G - C K_b is the second form of dL/da above.  Then [B]- and [
 and the upstream gradient.  The kernel's output T_b = sum_j e^{s_j - lse s} s_j gives dL/dt by the first form above; the
 backward takes the second, which does not subtract three f32 numbers of the size of a score.
 
-Which gradients exist: those of ``loss_ita`` with respect to the online features and the temperature.  The projection heads, the
-text stack and the ViT have no backward yet, and neither have the ITM and LM losses.
+Which gradients exist: those of ``loss_ita`` with respect to the online features and the temperature (above), and the backward of
+the heads on top of the two losses that have a forward: ``linear_backward`` (dX = dY · W and dW = dY^T · X on the backward forms
+of the GEMM, ``kernels.gemm_grad_input`` / ``gemm_grad_weight``), ``proj_head_backward`` (vision_proj / text_proj under the
+normalisation, from a gradient at the unit-norm feature to the head's parameters and its [CLS] input rows) and
+``itm_head_backward`` (the two-class cross-entropy to itm_head's parameters and its [CLS] rows).  The four loss models report
+them through ``forward(..., head_grads={})``; the text stack, the ViT and the LM loss have no backward.
 """
 from __future__ import annotations
 
@@ -126,3 +130,103 @@ def itc_terms_with_grads(grads, image_feat, text_feat, image_feat_m, text_feat_m
         g = torch.autograd.grad(terms[0], leaves)
     grads.update(image_feat=g[0], text_feat=g[1], temp=g[2])
     return tuple(t.detach() for t in terms)
+
+
+# ------------------------------------------------------------------------------------------------ head backward
+SPLIT_EXP = 10       # a scaled slice's largest magnitude lies in [2^10, 2^11): f16's third plane then stays above its subnormals
+
+
+def split3_planes(v32, dtype, dim):
+    """Exact three-plane split of f32 ``v32`` [R, C] into 16-bit operands: -> (hi, mid, lo, inv_scale) with
+    (hi + mid + lo) * inv_scale == v32, hi = T16(v), mid = T16(v - hi), lo = T16(v - hi - mid) of v = v32 * scale.  The scale is one
+    power of two per row (dim=1: inv_scale [R, 1]) or per column (dim=0: inv_scale [1, C]) that puts the slice's largest magnitude
+    into [2^10, 2^11) — gradients are 1e-3 .. 1e-7, where f16's third plane would underflow —, so scaling and unscaling are
+    exact.  bf16: 3 x 8 = 24 bits, exact for every f32; f16: 33 bits, exact for every element of at least 2^-12 of its slice's
+    largest (the third plane's ulp meets f16's smallest subnormal 2^-24 there)."""
+    amax = v32.abs().amax(dim=dim, keepdim=True)
+    _, e = torch.frexp(amax)                                     # amax = m * 2^e, m in [0.5, 1)
+    k = torch.where(amax > 0, SPLIT_EXP + 1 - e, torch.zeros_like(e)).clamp_(-120, 120)
+    one = torch.ones_like(amax)
+    v = v32 * torch.ldexp(one, k)
+    hi = v.to(dtype)
+    r = v - hi.float()
+    mid = r.to(dtype)
+    lo = (r - mid.float()).to(dtype)
+    return hi, mid, lo, torch.ldexp(one, -k)
+
+
+def _pad8(n):
+    return (n + 7) // 8 * 8
+
+
+def linear_backward(dy32, x16, w16, *, need_x=True, need_w=True, need_b=True):
+    """Backward of ``y = x16 · w16^T + b`` as the library's forward computes it -> (dx f32 [M, Kin], dw f32 [Nout, Kin], db f32
+    [Nout]); entries not asked for are None.  dy32 f32 [M, Nout]; x16 [M, Kin] and w16 [Nout, Kin]: the 16-bit tensors the forward
+    GEMM read, exact operands.  Only dy32 has to become 16-bit: its three exact planes (``split3_planes``) are concatenated along
+    the contraction axis — columns [hi | mid | lo] against [W; W; W] for dx, row blocks [hi; mid; lo] against [X; X; X] for dw,
+    the contraction padded with zeros to a multiple of 8 where the form needs it — so the error left is the f32 accumulation's.
+    db = dy32.sum(0), accumulated in f64."""
+    M, Nout = dy32.shape
+    Kin = w16.shape[1]
+    T = w16.dtype
+    if dy32.dtype != torch.float32 or x16.dtype != T or tuple(x16.shape) != (M, Kin) or w16.shape[0] != Nout:
+        raise K.VidilHipError(f"linear_backward: dy f32 [M, Nout], x [M, Kin] and w [Nout, Kin] of one 16-bit type expected, got "
+                              f"{dy32.dtype} {tuple(dy32.shape)}, {x16.dtype} {tuple(x16.shape)}, {w16.dtype} {tuple(w16.shape)}")
+    dev = dy32.device
+    Np = _pad8(Nout)
+    dx = dw = db = None
+    if need_x:
+        hi, mid, lo, inv = split3_planes(dy32, T, 1)                    # one scale per row of dy: a row of dx
+        a = torch.zeros((M, 3 * Np), dtype=T, device=dev)
+        w3 = torch.zeros((3 * Np, Kin), dtype=T, device=dev)
+        for i, plane in enumerate((hi, mid, lo)):
+            a[:, i * Np:i * Np + Nout] = plane
+            w3[i * Np:i * Np + Nout] = w16
+        dx = K.gemm_grad_input(a, w3) * inv
+    if need_w:
+        hi, mid, lo, inv = split3_planes(dy32, T, 0)                    # one scale per column of dy: a row of dw
+        a = torch.zeros((3 * M, Np), dtype=T, device=dev)
+        for i, plane in enumerate((hi, mid, lo)):
+            a[i * M:(i + 1) * M, :Nout] = plane
+        x3 = torch.cat([x16, x16, x16], 0).contiguous()
+        dw = K.gemm_grad_weight(a, x3)[:Nout] * inv.reshape(Nout, 1)
+    if need_b:
+        db = dy32.double().sum(0).float()
+    return dx, dw, db
+
+
+def normalize_backward(g, p):
+    """Gradient at the un-normalised rows p of f = p / ||p|| given g = dL/df: (g - f (f·g)) / ||p||."""
+    n = p.norm(dim=-1, keepdim=True)
+    f = p / n
+    return (g - f * (f * g).sum(-1, keepdim=True)) / n
+
+
+def cross_entropy_backward(logits, labels):
+    """d mean-cross-entropy / d logits = (softmax - onehot) / rows."""
+    d = torch.softmax(logits, dim=-1)
+    d[torch.arange(logits.shape[0], device=logits.device), labels] -= 1.0
+    return d / logits.shape[0]
+
+
+def proj_head_backward(g_feat, cls16, w16, b32, *, need_x=True):
+    """Backward of ``feat = normalize(mean_frames(cls16 · w16^T + b32))`` (vision_proj / text_proj under the ITC loss) ->
+    (dcls f32 [B*N, width], dw f32, db f32).  g_feat f32 [B, D]: the gradient at the unit-norm feature (``grads["image_feat"]``);
+    cls16 [B*N, width]: the 16-bit [CLS] rows the head read, N >= 1 frames per sample in sample-major order (N = 1: no mean).  The
+    un-normalised projection is recomputed with the forward's GEMM; every frame's row receives 1/N of its sample's gradient."""
+    B, D = g_feat.shape
+    rows = cls16.shape[0]
+    if rows % B:
+        raise K.VidilHipError(f"proj_head_backward: {rows} [CLS] rows for {B} features")
+    N = rows // B
+    cls16 = cls16.contiguous()
+    p = K.gemm(cls16, w16, b32, out=torch.empty((rows, D), dtype=torch.float32, device=cls16.device))
+    g_p = normalize_backward(g_feat, p.view(B, N, D).mean(dim=1) if N > 1 else p)
+    dy = (g_p / N).repeat_interleave(N, dim=0).contiguous() if N > 1 else g_p.contiguous()
+    return linear_backward(dy, cls16, w16, need_x=need_x)
+
+
+def itm_head_backward(logits32, labels, cls16, w16, *, need_x=True):
+    """Backward of ``cross_entropy(cls16 · w16^T + b, labels)`` over the pairs of the matching loss -> (dcls f32 [P, width], dw f32
+    [2, width], db f32 [2]); logits32 f32 [P, 2] as the forward reported them."""
+    return linear_backward(cross_entropy_backward(logits32.float(), labels).contiguous(), cls16.contiguous(), w16, need_x=need_x)
