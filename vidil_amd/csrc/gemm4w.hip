@@ -41,6 +41,7 @@
 
 #define VIDIL_EPI_LAZY 1   // gemm_epilogue.inc: bias / activation applied per stored quad, not to all accumulators up front
 #define VIDIL_EPI_NIT TM   // ... over the TM 32-row tiles of a wave's block
+#define VIDIL_EPI_VIEW16 C3   // ... reading the C3 loop's 16 x 16 accumulator tiles (acc16) where the kernel is the compensated form
 
 namespace {
 
@@ -71,9 +72,10 @@ __device__ __forceinline__ void glds16(const void* g, char* lds) {
 // C3 (round 5): the ERROR-COMPENSATED product of the parity precision mode computed INSIDE the K loop.  A holds the rows
 // [x_hi | x_lo | x_hi] (three planes of Kl = K / 3 columns: VIDIL_DT_SPLIT3's layout) and W the rows [W_hi | W_hi | W_lo], exactly
 // as for the K-tripled plain launch — but instead of walking 3 Kl columns (every x_hi and every W_hi tile through LDS twice),
-// one iteration fetches 32 logical columns of x_hi, x_lo, W_hi and W_lo — a 128-byte LDS row is [hi 64 B | lo 64 B], so the
-// fragment loader's k-steps 0, 1 are the hi halves and 2, 3 the lo halves — and issues the three products from the same
-// registers: (a_hi, w_hi), (a_hi, w_lo), (a_lo, w_hi) = 24 * TM MFMAs per 64 KiB of LDS-DMA where the plain loop issues 16 * TM:
+// one iteration fetches 32 logical columns of x_hi, x_lo, W_hi and W_lo — a 128-byte LDS row is [hi 64 B | lo 64 B], each half
+// exactly one k-step of v_mfma_f32_16x16x32 (gemm_epilogue.h Mma16) — and issues the three products from the same
+// registers: (a_hi, w_hi), (a_hi, w_lo), (a_lo, w_hi) = 48 * TM MFMAs of 16 cycles per 64 KiB of LDS-DMA where the plain loop issues
+// 16 * TM of 32 cycles:
 // two thirds of the operand traffic (HBM, LDS-DMA and fragment reads alike) per MFMA.  The summation order differs from the
 // K-tripled launch's (hi.hi + hi.lo + lo.hi per 32 columns instead of three passes over K), so a problem must take ONE of the two
 // forms at every size: vidil_gemm routes split_k launches here whatever M is (TM = 2 for small grids: same k order, same bits).
@@ -210,6 +212,10 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
 
   f32x16 accA[TM][2], accB[TM][2];   // output columns 0-63 / 64-127 of the wave's (32*TM) x 128 block
 #define ACC(i, j) ((j) < 2 ? accA[i][(j) & 1] : accB[i][(j) & 1])
+  // C3: the same block as (2*TM) x 8 tiles of 16 x 16 (v_mfma_f32_16x16x32: gemm_epilogue.h Mma16), 4 registers each — the plain
+  // loop never touches these and the C3 loop never touches the ones above, so each instantiation carries one set
+  f32x4 acc16A[2 * TM][4], acc16B[2 * TM][4];
+#define ACC16(mi, nj) ((nj) < 4 ? acc16A[mi][(nj) & 3] : acc16B[mi][(nj) & 3])
   float st_s[4], st_ss[4];
   f32x2 st_raw[4][4], st_sum[4];
 
@@ -229,20 +235,37 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
   constexpr int T_A = TM == 2 ? NFR + 1 : (ESZ == 2 ? VIDIL_4W_TA : 10);   // barrier A goes after this MFMA (developer sweep: -DVIDIL_4W_TA=17..29)
   constexpr int T_B = T_A + NPIECE * STEP;          // barrier B goes after this MFMA
   static_assert(T_B < NM - 2 && NFR <= T_A, "schedule");
-  // ---- C3 schedule: six (A k-step, W k-step) products per K-tile; fragments sets S0 = k-steps 0, 1 (hi), S1 = 2, 3 (lo)
-  //   pairs 0, 1: (0,0) (1,1)  hi.hi   | reads: fw[1] of THIS tile (deferred, see below), then S1 of this tile
-  //   pairs 2, 3: (0,2) (1,3)  hi.lo   | barrier A, the DMA pieces of tile g+2, barrier B
-  //   pairs 4, 5: (2,0) (3,1)  lo.hi   | S0 of tile g+1: the A fragments once pair 3 has issued (fa[0], fa[1] are dead),
-  //                                    |   fw[0] once pair 4 has issued; fw[1] feeds pair 5 to the end of the iteration, so the next
-  //                                    |   tile's fw[1] is read in the first slots of the next iteration (first needed by its pair 1)
-  constexpr int NM3 = 6 * NKS;
-  constexpr int C3_RS1 = 4;                                   // first slot of the S1 reads (after the deferred fw[1])
-  constexpr int C3_TA = C3_RS1 + NFR + 1;                     // barrier A: every read of this tile has been issued
-  constexpr int C3_STEP = TM == 4 ? 3 : 1;
+  // ---- C3 schedule, on v_mfma_f32_16x16x32 (16 matrix-pipe cycles each; under the socket's power cap the chip holds a higher
+  // clock on this shape than on 32x32x16 at equal cycles per FLOP: tools/micro/c3_loop_shapes.hip, profiles/c3_mfma16_ab.md).
+  // A plane's 64-byte half of the LDS row is ONE k-step of 32, so a K-tile is three products of NP = 8 * NMI MFMAs over the
+  // wave's NMI = 2*TM row tiles x 8 column tiles of 16, fragments ga[plane][row tile] / gw[plane][column tile].  Every product
+  // walks the column tiles outermost, so per accumulator the order is hi.hi, hi.lo, lo.hi in both tile heights (same bits):
+  //   product 0: ga[0] x gw[0]  hi.hi  | reads: gw[0][7] of THIS tile (deferred, see below), gw[1][*], ga[1][*]; barrier A
+  //   product 1: ga[0] x gw[1]  hi.lo  | the DMA pieces of tile g+2, one per C3_STEP MFMAs (96 matrix-pipe cycles apart at
+  //                                    |   TM = 4, 32 at TM = 2, as they were on 32x32x16); barrier B
+  //   product 2: ga[1] x gw[0]  lo.hi  | S0 of tile g+1: ga[0][*] in its first slots (product 1 has issued: ga[0] is dead), then
+  //                                    |   gw[0][q] right behind the last MFMA of column tile q; column tile 7 ends the
+  //                                    |   iteration, so the next tile's gw[0][7] is read in the first slot of the next
+  //                                    |   iteration (first needed by its MFMA 7 * NMI)
+  // At most one LDS read or one DMA piece behind an MFMA (a 16-cycle gap hides about two single-issue fillers).
+  constexpr int NMI = 2 * TM;
+  constexpr int NP = 8 * NMI;
+  constexpr int NM3 = 3 * NP;
+  constexpr int C3_TA = 1 + 8 + NMI;                          // barrier A: every read of this tile has been issued (slots 0 .. C3_TA - 1)
+  constexpr int C3_STEP = TM == 4 ? 6 : 2;
   constexpr int C3_TB = C3_TA + NPIECE * C3_STEP;             // barrier B after this MFMA
-  constexpr int C3_NA = (C3_TB + 2 > 4 * NKS ? C3_TB + 2 : 4 * NKS);      // first slot of the next tile's A fragments
-  constexpr int C3_NW = (C3_NA + 2 * TM > 5 * NKS ? C3_NA + 2 * TM : 5 * NKS);   // first slot of the next tile's fw[0]
-  static_assert(!C3 || (C3_NW + 4 <= NM3 && C3_TA + 1 <= 2 * NKS + NKS), "C3 schedule");
+  static_assert(!C3 || C3_TB + 1 < 2 * NP, "C3 schedule: tile g+1 has landed before product 2 reads it");
+  using Frag16 = typename Mma16<T>::Frag;
+  Frag16 ga[2][NMI], gw[2][8];
+  const int kq = lane >> 4, sw16 = ((lane & 15) >> 1) & 7;
+  const int a_off16 = (TM == 4 ? grp * SLOT : grp * 8192) + (lane & 15) * 128;    // (16-row tiles: 2 KiB apart)
+  const int w_off16 = (WSLOT + wc2) * SLOT + (lane & 15) * 128;
+  auto read_a16 = [&](const char* buf, int plane, int t) {
+    if constexpr (C3) ga[plane][t] = Mma16<T>::load(buf + a_off16 + t * 2048, plane, kq, sw16);
+  };
+  auto read_w16 = [&](const char* buf, int plane, int t) {
+    if constexpr (C3) gw[plane][t] = Mma16<T>::load(buf + w_off16 + t * 2048, plane, kq, sw16);
+  };
   auto read_frag = [&](const char* buf, int ks, int r) {     // r: 0-3 = W column tiles, 4-7 = A row tiles
 #if defined(VIDIL_4W_ABLATE) && (VIDIL_4W_ABLATE & 8)
     if (p.M > 0) return;     // developer ablation: no fragment reads
@@ -268,10 +291,18 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
     const int m0 = tile_m << MSH, n0 = tile_n << 8;
     // S0 of the tile's first K-tile (landed and visible since barrier B of the previous iteration / the start of the
     // stream).  Not fetched ahead across the epilogue: 64 live registers there cost more than this exposed LDS latency.
-    static_for<NFR>([&](auto f_tag) {
-      constexpr int f = decltype(f_tag)::value;
-      read_frag(smem + cb * BUF, f / NFK, f % NFK);
-    });
+    if constexpr (C3) {
+      static_for<NMI + 8>([&](auto f_tag) {
+        constexpr int f = decltype(f_tag)::value;
+        if constexpr (f < NMI) read_a16(smem + cb * BUF, 0, f);
+        else read_w16(smem + cb * BUF, 0, f - NMI);
+      });
+    } else {
+      static_for<NFR>([&](auto f_tag) {
+        constexpr int f = decltype(f_tag)::value;
+        read_frag(smem + cb * BUF, f / NFK, f % NFK);
+      });
+    }
     auto iteration = [&](auto first_tag, auto last_tag) {
       constexpr bool FIRST = decltype(first_tag)::value;   // first K-tile of an output tile: its first k-step starts from zero
       constexpr bool LAST = decltype(last_tag)::value;     // last K-tile: no fragment reads for a next one
@@ -389,17 +420,13 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
       const char* const nbuf = smem + (cb ^ 1) * BUF;
       static_for<NM3>([&](auto n_tag) {
         constexpr int n = decltype(n_tag)::value;
-        constexpr int pr = n / NKS, i = (n >> 2) % TM, j = n & 3;
-        constexpr int ka = pr == 0 ? 0 : pr == 1 ? 1 : pr == 2 ? 0 : pr == 3 ? 1 : pr == 4 ? 2 : 3;
-        constexpr int kw = pr == 0 ? 0 : pr == 1 ? 1 : pr == 2 ? 2 : pr == 3 ? 3 : pr == 4 ? 0 : 1;
-        if constexpr (FIRST && pr == 0) {
-          f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          ACC(i, j) = Mma<T>::mma(fw[kw][j], fa[ka][i], zero);
-        } else {
-          ACC(i, j) = Mma<T>::mma(fw[kw][j], fa[ka][i], ACC(i, j));
-        }
-        if constexpr (!FIRST && n < 4) read_frag(buf, 1, n);                                  // fw[1] of this tile (deferred)
-        if constexpr (n >= C3_RS1 && n < C3_RS1 + NFR) read_frag(buf, KH + (n - C3_RS1) / NFK, (n - C3_RS1) % NFK);   // S1
+        constexpr int pr = n / NP, nj = (n / NMI) & 7, mi = n % NMI;
+        constexpr int pa = pr == 2 ? 1 : 0, pw = pr == 1 ? 1 : 0;      // planes of the product: hi.hi, hi.lo, lo.hi
+        if constexpr (FIRST && pr == 0) Mma16<T>::mma_zero(gw[pw][nj], ga[pa][mi], ACC16(mi, nj));
+        else Mma16<T>::mma(gw[pw][nj], ga[pa][mi], ACC16(mi, nj));
+        if constexpr (!FIRST && n == 0) read_w16(buf, 0, 7);                                  // gw[0][7] of this tile (deferred)
+        if constexpr (n >= 1 && n < 9) read_w16(buf, 1, n - 1);                               // the lo planes of this tile
+        if constexpr (n >= 9 && n < 9 + NMI) read_a16(buf, 1, n - 9);
         if constexpr (n == C3_TA) {
           __builtin_amdgcn_s_waitcnt(0xC07F);                                    // lgkmcnt(0)
           __builtin_amdgcn_s_barrier();
@@ -422,12 +449,13 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
           asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPIECE) : "memory");
           __builtin_amdgcn_s_barrier();
         }
-        if constexpr (!LAST) {                                                   // S0 of the next K-tile, except fw[1]
-          if constexpr (n >= C3_NA && n < C3_NA + 2 * TM) read_frag(nbuf, (n - C3_NA) / TM, 4 + (n - C3_NA) % TM);   // fa[0][*], fa[1][*]
-          if constexpr (n >= C3_NW && n < C3_NW + 4) read_frag(nbuf, 0, n - C3_NW);                                  // fw[0][*]
+        if constexpr (!LAST) {                                                   // S0 of the next K-tile, except gw[0][7]
+          if constexpr (n >= 2 * NP && n < 2 * NP + NMI) read_a16(nbuf, 0, n - 2 * NP);
+          if constexpr (n >= 2 * NP + NMI && (n - 2 * NP) % NMI == 0) read_w16(nbuf, 0, (n - 2 * NP) / NMI - 1);   // column tile q is done
         }
         __builtin_amdgcn_sched_barrier(0);
       });
+      if constexpr (LAST) mma16_settle();     // (the epilogue reads accumulators the compiler does not know an MFMA has written)
       cb ^= 1;
     };
     if constexpr (C3) {
@@ -518,7 +546,9 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
       const char* const epb = ep + 4096;            // [bias of columns n_w .. n_w+127 | column sums of the same]: 2 x 512 B
       do {
 #define acc accA
+#define acc16 acc16A
 #include "gemm_epilogue.inc"
+#undef acc16
 #undef acc
       } while (0);
     }
@@ -527,7 +557,9 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
       const char* const epb = ep + 4096 + 256;
       do {
 #define acc accB
+#define acc16 acc16B
 #include "gemm_epilogue.inc"
+#undef acc16
 #undef acc
       } while (0);
     }
@@ -540,6 +572,7 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
     // outstanding" still implies every DMA piece older than the newest 16 has landed; pending stores only make the
     // wait stricter).  The first MFMAs of the next tile run while this tile's stores are acknowledged.
   }
+#undef ACC16
 #undef ACC
 }
 

@@ -88,5 +88,57 @@ struct Mma<fp8> {   // e4m3: v_mfma_scale_f32_32x32x64_f8f6f4 (scales 2^0), 64 k
   }
 };
 
+// The second operand trait (f16 / bf16 only): v_mfma_f32_16x16x32, used by the compensated (C3) main loop of gemm4w.hip.
+// There a 128-byte LDS row is [hi plane 64 B | lo plane 64 B] = 32 logical columns per plane, so ONE k-step covers a plane's
+// share of a K-tile: the lane's fragment is the 8 elements of row (lane & 15) of a 16-row tile, k-slot (lane >> 4) of the
+// plane's 64-byte half — logical 16-byte slot plane * 4 + (lane >> 4), at physical slot (logical ^ sw), sw = (row >> 1) & 7.
+// With SWAPPED operands (D = W_frag · A_frag^T) the lane leaves with 4 consecutive output columns of one row:
+//   acc16[mi][nj][e]: row = m_w + mi*16 + (lane & 15) ; col = n_w + nj*16 + (lane >> 4)*4 + e
+// Banks of the fragment read (ds_read_b128: four groups of 16 lanes, {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same
+// + 32; bank group of a 16-byte slot = (row & 1) * 8 + physical slot): a group holds every row 0..15 of the tile once, rows
+// {0-3, 12-15} with one k-slot and rows {4-11} with the next.  (row >> 1) is {0, 1, 6, 7} on the first set and {2, 3, 4, 5}
+// on the second, and k ^ {0, 1, 6, 7} and (k ^ 1) ^ {2, 3, 4, 5} = k ^ {3, 2, 5, 4} are disjoint: 8 distinct slots x 2 row
+// parities = 16 distinct bank groups per phase, as for the 32-row fragments.
+// The MFMA is issued as the instruction itself with its accumulator constrained to the AGPRs: through the builtin hipcc
+// spreads a wave's 64 four-register accumulators over both register files and shuffles them in every iteration (hundreds of
+// v_accvgpr copies, 28 instead of 16 cycles per MFMA in tools/micro/c3_loop_shapes.hip, and spills in the 256-row kernel).
+// The compiler therefore does not see an MFMA here: it still orders the fragment loads (s_waitcnt on the operands), but the
+// wait between the LAST MFMA of a tile and the first read of an accumulator is the caller's (mma16_settle).
+template <typename T> struct Mma16;
+// (XDL write -> VALU / VMEM read of the result: at most 18 wait states for this instruction; two s_nop 15 are 32)
+__device__ __forceinline__ void mma16_settle() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
+template <>
+struct Mma16<f16> {
+  typedef f16x8 Frag;
+  static __device__ __forceinline__ Frag load(const char* row, int plane, int kq, int sw) {
+    return *(const Frag*)(row + (((plane * 4 + kq) ^ sw) << 4));
+  }
+  static __device__ __forceinline__ void mma(const Frag& w, const Frag& a, f32x4& c) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(w), "v"(a));
+  }
+  static __device__ __forceinline__ void mma_zero(const Frag& w, const Frag& a, f32x4& c) {     // c = w . a^T (first k-step of a tile)
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(c) : "v"(w), "v"(a));
+  }
+};
+template <>
+struct Mma16<bf16> {
+  typedef bf16x8 Frag;
+  static __device__ __forceinline__ Frag load(const char* row, int plane, int kq, int sw) {
+    return *(const Frag*)(row + (((plane * 4 + kq) ^ sw) << 4));
+  }
+  static __device__ __forceinline__ void mma(const Frag& w, const Frag& a, f32x4& c) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(w), "v"(a));
+  }
+  static __device__ __forceinline__ void mma_zero(const Frag& w, const Frag& a, f32x4& c) {     // c = w . a^T (first k-step of a tile)
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(w), "v"(a));
+  }
+};
+template <>
+struct Mma16<fp8> {   // (never used: the compensated loop takes 16-bit operands; lets the kernel template name the type)
+  typedef i32x8 Frag;
+  static __device__ __forceinline__ void mma(const Frag&, const Frag&, f32x4&) {}
+  static __device__ __forceinline__ void mma_zero(const Frag&, const Frag&, f32x4&) {}
+};
+
 // T: operand type of A / W (only its size matters here: fp8 weights carry a per-column scale); TO: 16-bit output type.
 // st_s / st_ss (FOLD only): per row tile `it`, rstd and mean * rstd of the lane's row.

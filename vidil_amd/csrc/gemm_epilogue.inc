@@ -3,7 +3,7 @@
 // are final.  (A function taking the accumulator array by reference made hipcc keep the 128 accumulator registers in
 // scratch memory — 628 B per lane — so the body is shared as text, not as a function.)
 //
-// Names expected in scope: p (vidil_gemm_args), acc[4][2] (f32x16), m_w / n_w (first row / column of the wave's tile),
+// Names expected in scope: p (vidil_gemm_args), acc[4][2] (f32x16; with VIDIL_EPI_VIEW16 also acc16[8][4] (f32x4)), m_w / n_w (first row / column of the wave's tile),
 // ep (char*: the wave's private 8-KiB LDS scratch), st_s[4] / st_ss[4] (FOLD: rstd and mean*rstd per row tile),
 // lane, hi, l31, M, N, the template parameters T, TO (aliased as f16 / f16x4 / f16x8), EPI, ACT, FOLD, STATS, RLN
 // (residual LayerNorm: st_s / st_ss then describe the RESIDUAL rows) and ESZ = sizeof(T).  Early exits use `break`: the includer wraps this text in do { ... } while (0).
@@ -12,7 +12,34 @@
 //   acc[it][j][rq*4+e]: row = m_w + it*32 + l31 ; col = n_w + j*32 + rq*8 + hi*4 + e
 // so a lane owns 4 consecutive output columns of one row, and every store path first transposes through `ep` so that
 // global stores are 16 B per lane and 128-256 B contiguous per row.
+//
+// ACCUMULATOR VIEW.  The store paths below never index the accumulators themselves: a pass (32 rows x 64 columns of the wave's
+// tile) is the lane's EIGHT column quads, in two groups g of four (k), each with a row and a column-quad index (0..15) in
+// the pass — quadrow(it, g, q4) yields the four values of a group, vw_row(g) / vw_cq(g, k) say where they belong:
+//   32x32 form (V16 = false):  g = j, k = rq:  row l31,                 column quad g*8 + k*2 + hi      (8 bias quads per lane)
+//   16x16 form (V16 = true):   g = 16-row tile of the pass, k = nj:  row g*16 + (lane & 15),  column quad k*4 + (lane >> 4)
+//                              (acc16[2*it + g][k]: v_mfma_f32_16x16x32, gemm_epilogue.h Mma16; 4 bias quads per lane)
+// The includer selects the second form with VIDIL_EPI_VIEW16 (a constant expression) and provides `acc16` beside `acc`;
+// it is reached by the f32 (no row statistics), per-head and patch paths.  Per-element arithmetic is the same in both.
   if (n_w >= N) break;
+
+#ifdef VIDIL_EPI_VIEW16
+  constexpr bool V16 = VIDIL_EPI_VIEW16;
+  static_assert(!V16 || (!FOLD && !STATS && !RLN && ESZ == 2 && (EPI == VIDIL_EPI_F32 || EPI == VIDIL_EPI_HEADS || EPI == VIDIL_EPI_PATCH)),
+                "the 16x16 accumulator view: plain f32, per-head and patch epilogues");
+#else
+  constexpr bool V16 = false;
+#endif
+  const int l15 = lane & 15, kq = lane >> 4;
+  auto vw_row = [&](int g) {
+    if constexpr (V16) return g * 16 + l15;
+    else return l31;
+  };
+  auto vw_cq = [&](int g, int k) {
+    if constexpr (V16) return k * 4 + kq;
+    else return g * 8 + k * 2 + hi;
+  };
+  constexpr int NBG = V16 ? 1 : 2;     // groups of bias quads a lane holds: the 16x16 form's columns do not depend on g
 
 #ifdef VIDIL_EPI_NIT
   constexpr int NIT = VIDIL_EPI_NIT;   // 32-row tiles of the wave's block (gemm4w.hip: 4, or 2 in its 128-row-tile form)
@@ -47,9 +74,9 @@
     //  few dozen cycles instead of 16 global loads and an `s_waitcnt vmcnt(0)`)
     if (has_bias) {
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+      for (int j = 0; j < NBG; ++j)
 #pragma unroll
-        for (int rq = 0; rq < 4; ++rq) q_b[j][rq] = *(const f32x4*)(epb + (j * 32 + rq * 8 + hi * 4) * 4);
+        for (int rq = 0; rq < 4; ++rq) q_b[j][rq] = *(const f32x4*)(epb + vw_cq(j, rq) * 4 * 4);
     }
     if constexpr (FOLD || ESZ == 1) {     // (the folded LayerNorm's column sums, or the fp8 weights' per-column scales)
 #pragma unroll
@@ -61,10 +88,10 @@
   } else {
     if (has_bias) {
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+      for (int j = 0; j < NBG; ++j)
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-          const int col = n_w + j * 32 + rq * 8 + hi * 4;
+          const int col = n_w + vw_cq(j, rq) * 4;
           q_b[j][rq] = *(const f32x4*)(p.bias + (col + 4 <= N ? col : N - 4));
         }
     }
@@ -87,8 +114,12 @@
 #pragma unroll
     for (int pi = 0; pi < 8; ++pi) {
       const int rq = pi >> 1, e = (pi & 1) * 2;
-      w[pi] = f32x2{acc[it][j][rq * 4 + e], acc[it][j][rq * 4 + e + 1]};
-      const f32x2 b2 = {q_b[j][rq][e], q_b[j][rq][e + 1]};
+#ifdef VIDIL_EPI_VIEW16
+      if constexpr (V16) w[pi] = f32x2{acc16[it * 2 + j][rq][e], acc16[it * 2 + j][rq][e + 1]};
+      else
+#endif
+        w[pi] = f32x2{acc[it][j][rq * 4 + e], acc[it][j][rq * 4 + e + 1]};
+      const f32x2 b2 = {q_b[V16 ? 0 : j][rq][e], q_b[V16 ? 0 : j][rq][e + 1]};
       if constexpr (FOLD) {
         const f32x2 c2 = {q_c[j][rq][e], q_c[j][rq][e + 1]};
         w[pi] = pk_fma(w[pi], pk_splat(st_s[it]), pk_fma(pk_splat(-st_ss[it]), c2, b2));
@@ -211,7 +242,8 @@
           for (int rq = 0; rq < 4; ++rq) {
             const f32x4 q = q4[rq];
             const f16x4 v = {Elt<TO>::from_f32(q[0]), Elt<TO>::from_f32(q[1]), Elt<TO>::from_f32(q[2]), Elt<TO>::from_f32(q[3])};
-            *(f16x4*)(ep + l31 * ROWB + (j * 32 + rq * 8 + hi * 4) * 2) = v;
+            if constexpr (V16) *(f16x4*)(ep + vw_row(j) * ROWB + vw_cq(j, rq) * 4 * 2) = v;
+            else *(f16x4*)(ep + l31 * ROWB + (j * 32 + rq * 8 + hi * 4) * 2) = v;
           }
         }
         int b = mb / p.T, t = mb - b * p.T;
@@ -237,6 +269,28 @@
     }
     if (part == 2 && p.NP != 0) {   // (NP == 0: V stays row-major and takes the 16-B store path of K below)
       // V^T: element (row m, column d) goes to VT[b][h][d][t_off+t]; consecutive lanes = consecutive t
+      if constexpr (V16) {      // (the lane's row depends on the group: one (image, token) per group)
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+#pragma unroll
+          for (int g = 0; g < 2; ++g) {
+            const int m = m_w + it * 32 + vw_row(g);
+            if (m < M) {
+              const int b = m / p.T, t = m - b * p.T;
+              f16* dst = (f16*)p.vt + (((size_t)b * p.H + head) * 64) * (size_t)p.NP + vt_pos(p.t_off + t);
+              f32x4 q4[4];
+              quadrow(it, g, q4);
+#pragma unroll
+              for (int k = 0; k < 4; ++k) {
+                const f32x4 q = q4[k];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dst[(size_t)(vw_cq(g, k) * 4 + e) * p.NP] = Elt<TO>::from_f32(q[e]);
+              }
+            }
+          }
+        }
+        break;
+      }
 #pragma unroll
       for (int it = 0; it < NIT; ++it) {
         const int m = m_w + it * 32 + l31;
@@ -326,7 +380,9 @@
             const f32x4 q = q4[rq];
             const f32x2 q01 = f32x2{q[0], q[1]} * pk_splat(scale), q23 = f32x2{q[2], q[3]} * pk_splat(scale);   // (two v_pk_mul_f32; x * 1 is exact)
             const f16x4 v = {Elt<TO>::from_f32(q01[0]), Elt<TO>::from_f32(q01[1]), Elt<TO>::from_f32(q23[0]), Elt<TO>::from_f32(q23[1])};
-            *(f16x4*)(buf + l31 * 128 + (((j * 4 + rq) ^ (l31 & 7)) << 4) + hi * 8) = v;
+            // (16-byte chunk = column quad >> 1, its half = column quad & 1)
+            if constexpr (V16) *(f16x4*)(buf + (j * 16 + l15) * 128 + (((rq * 2 + (kq >> 1)) ^ (l15 & 7)) << 4) + (kq & 1) * 8) = v;
+            else *(f16x4*)(buf + l31 * 128 + (((j * 4 + rq) ^ (l31 & 7)) << 4) + hi * 8) = v;
           }
         }
       };
@@ -574,13 +630,13 @@
         if (pass + AH < NIT) load_rows(addb[(pass + AH) % (AH + 1)]);
         {
           const int it = pass;
-          const int lr = l31;
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
+            const int lr = vw_row(j);
             f32x4 q4[4];
             quadrow(it, j, q4);
 #pragma unroll
-            for (int rq = 0; rq < 4; ++rq) *(f32x4*)(ep + lr * 256 + (((j * 8 + rq * 2 + hi) ^ (lr & 7)) << 4)) = q4[rq];
+            for (int rq = 0; rq < 4; ++rq) *(f32x4*)(ep + lr * 256 + ((vw_cq(j, rq) ^ (lr & 7)) << 4)) = q4[rq];
           }
         }
         f32x4 vrow[8];
@@ -683,13 +739,13 @@
       if (pass + AH < NIT) load_rows(pass + AH, addb[(pass + AH) % (AH + 1)]);
       {
         const int it = pass;
-        const int lr = l31;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
+          const int lr = vw_row(j);
           f32x4 q4[4];
           quadrow(it, j, q4);
 #pragma unroll
-          for (int rq = 0; rq < 4; ++rq) *(f32x4*)(ep + lr * 256 + (((j * 8 + rq * 2 + hi) ^ (lr & 7)) << 4)) = q4[rq];
+          for (int rq = 0; rq < 4; ++rq) *(f32x4*)(ep + lr * 256 + ((vw_cq(j, rq) ^ (lr & 7)) << 4)) = q4[rq];
         }
       }
       const int ch = lane & 15;
