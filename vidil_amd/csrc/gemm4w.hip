@@ -16,6 +16,11 @@
 // layout as in gemm256.hip (128-B rows, 16-B slot XOR (row>>1)&7, filled by global_load_lds_dwordx4); then 4 x 8 KiB of
 // private epilogue scratch (the ring is never idle here, so the transposition cannot borrow it).
 //
+// 16-bit operands (plain and compensated) run the iteration on v_mfma_f32_16x16x32 — same K-tile, ring, barriers and DMA stream, 2 x 8
+// x 2*TM MFMAs of 16 cycles per plain K-tile instead of 16 x TM of 32 (iteration_p16 / iteration_c3 and the schedule comments at
+// P16_TA / C3_TA): under the socket's power cap the chip holds a higher clock on that shape (profiles/gemm4w_mfma16_ab.md).  The
+// iteration described here is the fp8 one, and the shape of the other two.
+//
 // One iteration = one K-tile = 16*KS MFMAs per wave, fragments of the tile's first half of k-steps (S0) already in
 // registers:
 //     MFMAs of S0      | after each of the first ones: one fragment read of S1 (second half of k-steps, same tile)
@@ -41,7 +46,7 @@
 
 #define VIDIL_EPI_LAZY 1   // gemm_epilogue.inc: bias / activation applied per stored quad, not to all accumulators up front
 #define VIDIL_EPI_NIT TM   // ... over the TM 32-row tiles of a wave's block
-#define VIDIL_EPI_VIEW16 C3   // ... reading the C3 loop's 16 x 16 accumulator tiles (acc16) where the kernel is the compensated form
+#define VIDIL_EPI_VIEW16 (ESZ_OF_T == 2)   // ... reading the 16 x 16 accumulator tiles (acc16) of the 16-bit loops; fp8 keeps the 32 x 32 form
 
 namespace {
 
@@ -210,13 +215,14 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
     }
   };
 
-  f32x16 accA[TM][2], accB[TM][2];   // output columns 0-63 / 64-127 of the wave's (32*TM) x 128 block
+  f32x16 accA[TM][2], accB[TM][2];   // fp8: output columns 0-63 / 64-127 of the wave's (32*TM) x 128 block
 #define ACC(i, j) ((j) < 2 ? accA[i][(j) & 1] : accB[i][(j) & 1])
-  // C3: the same block as (2*TM) x 8 tiles of 16 x 16 (v_mfma_f32_16x16x32: gemm_epilogue.h Mma16), 4 registers each — the plain
-  // loop never touches these and the C3 loop never touches the ones above, so each instantiation carries one set
+  // 16-bit operands: the same block as (2*TM) x 8 tiles of 16 x 16 (v_mfma_f32_16x16x32: gemm_epilogue.h Mma16), 4 registers each — the
+  // fp8 loop never touches these and the 16-bit loops never touch the ones above, so each instantiation carries one set
   f32x4 acc16A[2 * TM][4], acc16B[2 * TM][4];
 #define ACC16(mi, nj) ((nj) < 4 ? acc16A[mi][(nj) & 3] : acc16B[mi][(nj) & 3])
-  float st_s[4], st_ss[4];
+  float st_s[4], st_ss[4];             // rstd, mean * rstd of row it*32 + (lane & 31) ...
+  float st16_s[4], st16_ss[4];         // ... and of row it*32 + ((lane & 31) ^ 16): the other row this lane has in the 16 x 16 view (FOLD)
   f32x2 st_raw[4][4], st_sum[4];
 
   const int sw = (l31 >> 1) & 7;
@@ -228,13 +234,11 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
   constexpr int NM = NKS * KS;         // MFMAs per K-tile per wave
   constexpr int NFK = 4 + TM;          // fragments per k-step: 4 W column tiles, TM A row tiles
   constexpr int NFR = KH * NFK;        // fragments per set
-  constexpr int STEP = (ESZ == 2 && TM == 4) ? 2 : 1;   // MFMAs per DMA piece
-#ifndef VIDIL_4W_TA
-#define VIDIL_4W_TA 21
-#endif
-  constexpr int T_A = TM == 2 ? NFR + 1 : (ESZ == 2 ? VIDIL_4W_TA : 10);   // barrier A goes after this MFMA (developer sweep: -DVIDIL_4W_TA=17..29)
+  // (the 32x32 loop serves fp8 operands only: 32 MFMAs of 64 cycles per K-tile, one DMA piece behind each of 16 of them)
+  constexpr int STEP = 1;                           // MFMAs per DMA piece
+  constexpr int T_A = 10;                           // barrier A goes after this MFMA
   constexpr int T_B = T_A + NPIECE * STEP;          // barrier B goes after this MFMA
-  static_assert(T_B < NM - 2 && NFR <= T_A, "schedule");
+  static_assert(ESZ == 2 || (T_B < NM - 2 && NFR <= T_A), "schedule");
   // ---- C3 schedule, on v_mfma_f32_16x16x32 (16 matrix-pipe cycles each; under the socket's power cap the chip holds a higher
   // clock on this shape than on 32x32x16 at equal cycles per FLOP: tools/micro/c3_loop_shapes.hip, profiles/c3_mfma16_ab.md).
   // A plane's 64-byte half of the LDS row is ONE k-step of 32, so a K-tile is three products of NP = 8 * NMI MFMAs over the
@@ -255,16 +259,28 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
   constexpr int C3_STEP = TM == 4 ? 6 : 2;
   constexpr int C3_TB = C3_TA + NPIECE * C3_STEP;             // barrier B after this MFMA
   static_assert(!C3 || C3_TB + 1 < 2 * NP, "C3 schedule: tile g+1 has landed before product 2 reads it");
+  // ---- plain 16-bit schedule, on the same instruction and register set: a K-tile of 64 k is TWO products of NP MFMAs (the same
+  // 2,048 / 1,024 matrix-pipe cycles as 16 * TM MFMAs of 32x32x16), column tiles outermost:
+  //   product 0: ga[0] x gw[0]  k 0-31   | reads: gw[1][*], ga[1][*] (slots 0 .. 7 + NMI); barrier A a few MFMAs behind the last
+  //                                      |   read (the wait then finds it landed, as T_A did in the 32x32x16 loop); then the DMA
+  //   product 1: ga[1] x gw[1]  k 32-63  |   pieces of tile g+2, one per P16_STEP MFMAs, running on into product 1; barrier B;
+  //                                      |   k 0-31 of tile g+1: ga[0][*], then gw[0][*] in the order product 0 needs them
+  // At most one LDS read or one DMA piece behind an MFMA.  Barrier B sits at 79 % (TM = 4) / 80 % (TM = 2) of the iteration,
+  // where the 32x32x16 loop had it (84 % / 81 %): tile g+1 gets the same ~1.04 iterations between its last piece and the wait.
+  constexpr int P16_TA = 8 + NMI + (TM == 4 ? 4 : 2);
+  constexpr int P16_STEP = TM == 4 ? 5 : 3;
+  constexpr int P16_TB = P16_TA + NPIECE * P16_STEP;            // barrier B after this MFMA
+  static_assert(P16_TB + 1 >= NP && P16_TB + 2 + NMI + 8 <= 2 * NP, "plain 16-bit schedule: the next tile's reads follow barrier B inside product 1");
   using Frag16 = typename Mma16<T>::Frag;
   Frag16 ga[2][NMI], gw[2][8];
   const int kq = lane >> 4, sw16 = ((lane & 15) >> 1) & 7;
   const int a_off16 = (TM == 4 ? grp * SLOT : grp * 8192) + (lane & 15) * 128;    // (16-row tiles: 2 KiB apart)
   const int w_off16 = (WSLOT + wc2) * SLOT + (lane & 15) * 128;
   auto read_a16 = [&](const char* buf, int plane, int t) {
-    if constexpr (C3) ga[plane][t] = Mma16<T>::load(buf + a_off16 + t * 2048, plane, kq, sw16);
+    if constexpr (ESZ == 2) ga[plane][t] = Mma16<T>::load(buf + a_off16 + t * 2048, plane, kq, sw16);
   };
   auto read_w16 = [&](const char* buf, int plane, int t) {
-    if constexpr (C3) gw[plane][t] = Mma16<T>::load(buf + w_off16 + t * 2048, plane, kq, sw16);
+    if constexpr (ESZ == 2) gw[plane][t] = Mma16<T>::load(buf + w_off16 + t * 2048, plane, kq, sw16);
   };
   auto read_frag = [&](const char* buf, int ks, int r) {     // r: 0-3 = W column tiles, 4-7 = A row tiles
 #if defined(VIDIL_4W_ABLATE) && (VIDIL_4W_ABLATE & 8)
@@ -291,7 +307,7 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
     const int m0 = tile_m << MSH, n0 = tile_n << 8;
     // S0 of the tile's first K-tile (landed and visible since barrier B of the previous iteration / the start of the
     // stream).  Not fetched ahead across the epilogue: 64 live registers there cost more than this exposed LDS latency.
-    if constexpr (C3) {
+    if constexpr (ESZ == 2) {
       static_for<NMI + 8>([&](auto f_tag) {
         constexpr int f = decltype(f_tag)::value;
         if constexpr (f < NMI) read_a16(smem + cb * BUF, 0, f);
@@ -303,7 +319,7 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
         read_frag(smem + cb * BUF, f / NFK, f % NFK);
       });
     }
-    auto iteration = [&](auto first_tag, auto last_tag) {
+    auto iteration = [&](auto first_tag, auto last_tag) {      // fp8 operands, v_mfma_scale_f32_32x32x64_f8f6f4
       constexpr bool FIRST = decltype(first_tag)::value;   // first K-tile of an output tile: its first k-step starts from zero
       constexpr bool LAST = decltype(last_tag)::value;     // last K-tile: no fragment reads for a next one
       const char* const buf = smem + cb * BUF;
@@ -349,6 +365,66 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
             glds16(src, smem + RING_BYTES + wave * 8192 + 4096);
           }
         }
+        if constexpr (n == T_B + 1) {
+          // tile g+1 has landed once nothing older than this iteration's 16 DMA pieces is in flight
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPIECE) : "memory");
+          __builtin_amdgcn_s_barrier();
+        }
+        if constexpr (n > T_B + 1 && !LAST) {                                    // S0 of the next K-tile
+          constexpr int SLOTS = NM - T_B - 2;
+          constexpr int PER = (NFR + SLOTS - 1) / SLOTS;
+          constexpr int s = n - T_B - 2;
+          static_for<PER>([&](auto q_tag) {
+            constexpr int f = s * PER + decltype(q_tag)::value;
+            if constexpr (f < NFR) read_frag(nbuf, f / NFK, f % NFK);
+          });
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      cb ^= 1;
+    };
+    // The plain 16-bit K-tile on v_mfma_f32_16x16x32: the two 64-byte halves of the LDS row are the k-steps 0-31 and 32-63,
+    // product 0 = ga[0] x gw[0], product 1 = ga[1] x gw[1], k ascending per accumulator as in the 32x32x16 loop (same bits as
+    // gemm256: tests/test_gemm4w_gpu.py, tests/test_gemm4w_mfma16_gpu.py).  Slots: see P16_TA / P16_TB above.
+    auto iteration_p16 = [&](auto first_tag, auto last_tag) {
+      constexpr bool FIRST = decltype(first_tag)::value;
+      constexpr bool LAST = decltype(last_tag)::value;
+      const char* const buf = smem + cb * BUF;
+      const char* const nbuf = smem + (cb ^ 1) * BUF;
+      static_for<2 * NP>([&](auto n_tag) {
+        constexpr int n = decltype(n_tag)::value;
+        constexpr int pl = n / NP, nj = (n / NMI) & 7, mi = n % NMI;
+        if constexpr (FIRST && pl == 0) Mma16<T>::mma_zero(gw[0][nj], ga[0][mi], ACC16(mi, nj));
+        else Mma16<T>::mma(gw[pl][nj], ga[pl][mi], ACC16(mi, nj));
+        if constexpr (n < 8) read_w16(buf, 1, n);                                             // k 32-63 of this tile
+        if constexpr (n >= 8 && n < 8 + NMI) read_a16(buf, 1, n - 8);
+        if constexpr (n == P16_TA) {
+          __builtin_amdgcn_s_waitcnt(0xC07F);                                    // lgkmcnt(0)
+          __builtin_amdgcn_s_barrier();
+        }
+        if constexpr (n > P16_TA && n <= P16_TB && (n - P16_TA - 1) % P16_STEP == 0) {
+          constexpr int pc = (n - P16_TA - 1) / P16_STEP;
+          issue_piece(pc);
+          if constexpr (pc == NPIECE - 1) head_advance();
+        }
+        if constexpr (BIAS_LDS && LAST && n == 0) {
+          // The epilogue's per-column vectors — bias, and the folded LayerNorm's column sums — for this wave's 128 columns,
+          // fetched by ONE LDS-DMA instruction (lanes 0-31: bias, lanes 32-63: column sums, 16 B each) into the upper half
+          // of the wave's epilogue scratch while the last K-tile is still being multiplied.  Loaded by the epilogue itself
+          // (16 global loads per 64-column half) they cost an `s_waitcnt vmcnt(0)` — L2 latency, plus a drain of every store
+          // of the previous half and of the DMA stream — twice per tile with the matrix pipe idle.  Older than this
+          // iteration's DMA pieces, so barrier B's counted wait covers it (as for the row partials below).
+          if (p.bias != nullptr || FOLD) {     // (uniform)
+            int lane_s;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_s));
+            int col = n0 + wc2 * 128 + (lane_s & 31) * 4;
+            col = col + 4 <= N ? col : N - 4;      // (columns past N are never stored; N >= 4)
+            const float* v0 = p.bias != nullptr ? p.bias : p.ln_colsum;
+            const float* v1 = FOLD ? p.ln_colsum : v0;
+            const float* src = (lane_s < 32 ? v0 : v1) + col;
+            glds16(src, smem + RING_BYTES + wave * 8192 + 4096);
+          }
+        }
         if constexpr (ROWSTAT && LAST && n == 0) {
           // this half-wave's share of the producer's row partials (half-wave (wc2, hi) takes parts w, w+4, w+8, w+12 with
           // w = wc2 + 2*hi): issued at the top of the LAST K-tile (carried from the top of the output tile they were spilled
@@ -378,12 +454,12 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
             }
           }
         }
-        if constexpr (n == T_B + 1) {
+        if constexpr (n == P16_TB + 1) {
           // tile g+1 has landed once nothing older than this iteration's 16 DMA pieces is in flight
           asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPIECE) : "memory");
           __builtin_amdgcn_s_barrier();
         }
-        if constexpr (ROWSTAT && LAST && n == T_B + 2) {
+        if constexpr (ROWSTAT && LAST && n == P16_TB + 2) {
           // the half-wave's sums, in gemm256's order: parts {w, w+8} then {w+4, w+12}; parts past the end count as zero
           int lane_s;
           asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_s));
@@ -400,17 +476,14 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
                                (st_raw[it][0][1] + st_raw[it][2][1]) + (st_raw[it][1][1] + st_raw[it][3][1])};
           }
         }
-        if constexpr (n > T_B + 1 && !LAST) {                                    // S0 of the next K-tile
-          constexpr int SLOTS = NM - T_B - 2;
-          constexpr int PER = (NFR + SLOTS - 1) / SLOTS;
-          constexpr int s = n - T_B - 2;
-          static_for<PER>([&](auto q_tag) {
-            constexpr int f = s * PER + decltype(q_tag)::value;
-            if constexpr (f < NFR) read_frag(nbuf, f / NFK, f % NFK);
-          });
+        if constexpr (n > P16_TB + 1 && !LAST) {                                 // k 0-31 of the next K-tile: ga[0] / gw[0] died with product 0
+          constexpr int s = n - P16_TB - 2;
+          if constexpr (s < NMI) read_a16(nbuf, 0, s);
+          else if constexpr (s < NMI + 8) read_w16(nbuf, 0, s - NMI);
         }
         __builtin_amdgcn_sched_barrier(0);
       });
+      if constexpr (LAST) mma16_settle();     // (the epilogue reads accumulators the compiler does not know an MFMA has written)
       cb ^= 1;
     };
     auto iteration_c3 = [&](auto first_tag, auto last_tag) {
@@ -466,6 +539,14 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
         for (int u = 2; u < nk; ++u) iteration_c3(std::false_type{}, std::false_type{});
         iteration_c3(std::false_type{}, std::true_type{});
       }
+    } else if constexpr (ESZ == 2) {
+      if (nk == 1) {
+        iteration_p16(std::true_type{}, std::true_type{});
+      } else {
+        iteration_p16(std::true_type{}, std::false_type{});
+        for (int u = 2; u < nk; ++u) iteration_p16(std::false_type{}, std::false_type{});
+        iteration_p16(std::false_type{}, std::true_type{});
+      }
     } else if (nk == 1) {
       iteration(std::true_type{}, std::true_type{});
     } else {
@@ -516,6 +597,19 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const vidil_gemm_args p) {
         const float rstd = 1.0f / sqrtf(var + p.ln_eps);
         st_s[it] = rstd;
         st_ss[it] = mean * rstd;
+      }
+      if constexpr (FOLD) {
+        // the fold multiplies accumulators in the 16 x 16 view: group g of row tile `it` is row g*16 + (lane & 15) of that tile.
+        // Its pair is this lane's own where bit 4 of the lane equals g and lane ^ 16's otherwise: 8 lane permutes per output
+        // tile, issued together (one LDS round trip), and a select where a quad is formed (gemm_epilogue.inc: quadrow).
+        // (ds_swizzle, bit mode: and 0x1F, or 0, xor 0x10 — no address operand.  __shfl_xor forms its address from a lane id of
+        //  its own, which the compiler computes once at the top of the kernel and spills across the main loop: its reload here
+        //  was an `s_waitcnt vmcnt(0)` once per tile.)
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+          st16_s[it] = __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, st_s[it]), 0x401F));
+          st16_ss[it] = __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, st_ss[it]), 0x401F));
+        }
       }
       if constexpr (RLN) {   // (the f32 epilogue transposes through ALL 8 KiB of a wave's scratch: late readers first)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

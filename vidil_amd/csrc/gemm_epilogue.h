@@ -88,9 +88,9 @@ struct Mma<fp8> {   // e4m3: v_mfma_scale_f32_32x32x64_f8f6f4 (scales 2^0), 64 k
   }
 };
 
-// The second operand trait (f16 / bf16 only): v_mfma_f32_16x16x32, used by the compensated (C3) main loop of gemm4w.hip.
-// There a 128-byte LDS row is [hi plane 64 B | lo plane 64 B] = 32 logical columns per plane, so ONE k-step covers a plane's
-// share of a K-tile: the lane's fragment is the 8 elements of row (lane & 15) of a 16-row tile, k-slot (lane >> 4) of the
+// The second operand trait (f16 / bf16 only): v_mfma_f32_16x16x32, used by both 16-bit main loops of gemm4w.hip.  In the compensated
+// (C3) loop a 128-byte LDS row is [hi plane 64 B | lo plane 64 B] = 32 logical columns per plane, so ONE k-step covers a plane's
+// share of a K-tile; in the plain loop the two halves ("planes" 0 and 1) are k 0-31 and k 32-63 of a K-tile of 64.  The lane's fragment is the 8 elements of row (lane & 15) of a 16-row tile, k-slot (lane >> 4) of the
 // plane's 64-byte half — logical 16-byte slot plane * 4 + (lane >> 4), at physical slot (logical ^ sw), sw = (row >> 1) & 7.
 // With SWAPPED operands (D = W_frag · A_frag^T) the lane leaves with 4 consecutive output columns of one row:
 //   acc16[mi][nj][e]: row = m_w + mi*16 + (lane & 15) ; col = n_w + nj*16 + (lane >> 4)*4 + e

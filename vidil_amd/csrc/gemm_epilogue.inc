@@ -19,14 +19,17 @@
 //   32x32 form (V16 = false):  g = j, k = rq:  row l31,                 column quad g*8 + k*2 + hi      (8 bias quads per lane)
 //   16x16 form (V16 = true):   g = 16-row tile of the pass, k = nj:  row g*16 + (lane & 15),  column quad k*4 + (lane >> 4)
 //                              (acc16[2*it + g][k]: v_mfma_f32_16x16x32, gemm_epilogue.h Mma16; 4 bias quads per lane)
-// The includer selects the second form with VIDIL_EPI_VIEW16 (a constant expression) and provides `acc16` beside `acc`;
-// it is reached by the f32 (no row statistics), per-head and patch paths.  Per-element arithmetic is the same in both.
+// The includer selects the second form with VIDIL_EPI_VIEW16 (a constant expression) and provides `acc16` beside `acc` and, for
+// FOLD, st16_s[4] / st16_ss[4]: the row statistics of the OTHER row a lane has in this view (row l31 ^ 16 of row tile `it`, fetched
+// by lane permute; group g of the lane is row g*16 + (lane & 15)).  The bias AND column-sum quads follow vw_cq.  Everything behind
+// the transposition through `ep` (residual, residual LayerNorm, row partials, 16-bit copy) works in the post-transposition lane
+// layout and does not depend on the view.
+// Per-element arithmetic and its order are the same in both forms.
   if (n_w >= N) break;
 
 #ifdef VIDIL_EPI_VIEW16
   constexpr bool V16 = VIDIL_EPI_VIEW16;
-  static_assert(!V16 || (!FOLD && !STATS && !RLN && ESZ == 2 && (EPI == VIDIL_EPI_F32 || EPI == VIDIL_EPI_HEADS || EPI == VIDIL_EPI_PATCH)),
-                "the 16x16 accumulator view: plain f32, per-head and patch epilogues");
+  static_assert(!V16 || ESZ == 2, "the 16x16 accumulator view: 16-bit operands");
 #else
   constexpr bool V16 = false;
 #endif
@@ -39,7 +42,11 @@
     if constexpr (V16) return k * 4 + kq;
     else return g * 8 + k * 2 + hi;
   };
-  constexpr int NBG = V16 ? 1 : 2;     // groups of bias quads a lane holds: the 16x16 form's columns do not depend on g
+  // (FOLD in the 16x16 form: st_s / st_ss describe row l31 = (kq & 1) * 16 + l15 of a row tile, the includer's st16_s / st16_ss row l31 ^ 16)
+#ifdef VIDIL_EPI_VIEW16
+  const bool own_row[2] = {(kq & 1) == 0, (kq & 1) == 1};
+#endif
+  constexpr int NBG = V16 ? 1 : 2;    // groups of bias quads a lane holds: the 16x16 form's columns do not depend on g
 
 #ifdef VIDIL_EPI_NIT
   constexpr int NIT = VIDIL_EPI_NIT;   // 32-row tiles of the wave's block (gemm4w.hip: 4, or 2 in its 128-row-tile form)
@@ -80,9 +87,9 @@
     }
     if constexpr (FOLD || ESZ == 1) {     // (the folded LayerNorm's column sums, or the fp8 weights' per-column scales)
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+      for (int j = 0; j < NBG; ++j)
 #pragma unroll
-        for (int rq = 0; rq < 4; ++rq) q_c[j][rq] = *(const f32x4*)(epb + 512 + (j * 32 + rq * 8 + hi * 4) * 4);
+        for (int rq = 0; rq < 4; ++rq) q_c[j][rq] = *(const f32x4*)(epb + 512 + vw_cq(j, rq) * 4 * 4);
     }
 #endif
   } else {
@@ -98,10 +105,10 @@
     if constexpr (FOLD || ESZ == 1) {
       const float* const cvec = FOLD ? p.ln_colsum : p.w_scale;
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+      for (int j = 0; j < NBG; ++j)
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-          const int col = n_w + j * 32 + rq * 8 + hi * 4;
+          const int col = n_w + vw_cq(j, rq) * 4;
           q_c[j][rq] = *(const f32x4*)(cvec + (col + 4 <= N ? col : N - 4));
         }
     }
@@ -121,8 +128,12 @@
         w[pi] = f32x2{acc[it][j][rq * 4 + e], acc[it][j][rq * 4 + e + 1]};
       const f32x2 b2 = {q_b[V16 ? 0 : j][rq][e], q_b[V16 ? 0 : j][rq][e + 1]};
       if constexpr (FOLD) {
-        const f32x2 c2 = {q_c[j][rq][e], q_c[j][rq][e + 1]};
-        w[pi] = pk_fma(w[pi], pk_splat(st_s[it]), pk_fma(pk_splat(-st_ss[it]), c2, b2));
+        const f32x2 c2 = {q_c[V16 ? 0 : j][rq][e], q_c[V16 ? 0 : j][rq][e + 1]};
+#ifdef VIDIL_EPI_VIEW16
+        if constexpr (V16) w[pi] = pk_fma(w[pi], pk_splat(own_row[j] ? st_s[it] : st16_s[it]), pk_fma(pk_splat(-(own_row[j] ? st_ss[it] : st16_ss[it])), c2, b2));
+        else
+#endif
+          w[pi] = pk_fma(w[pi], pk_splat(st_s[it]), pk_fma(pk_splat(-st_ss[it]), c2, b2));
       } else if constexpr (ESZ == 1) {
         const f32x2 c2 = {q_c[j][rq][e], q_c[j][rq][e + 1]};
         w[pi] = pk_fma(w[pi], c2, b2);
@@ -473,13 +484,22 @@
             rows4(std::false_type{});
           }
         } else {
-          int b = m_first / p.T, t = m_first - b * p.T;
+          // (the divisor made opaque: the reciprocal of p.T is tile-invariant, and hoisted out of the tile loop it is spilled across
+          //  the main loop — its reload here is a VMEM load waited for with vmcnt(0); see inv_k in gemm4w.hip)
+          int tdiv = p.T;
+          asm volatile("" : "+s"(tdiv));
+          int b = m_first / tdiv, t = m_first - b * tdiv;
           const size_t hd = (size_t)p.H * 64;
+          // (the lane's column offset as a 64-bit value formed HERE: as `+ ch * 8` its zero upper half is a constant the compiler
+          //  keeps in a register from the top of the kernel, and the pair was spilled across the main loop as a unit)
+          uint32_t coff_hi;
+          asm volatile("v_mov_b32 %0, 0" : "=v"(coff_hi));
+          const size_t coff = ((size_t)coff_hi << 32) | (uint32_t)(ch * 8);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int m = m_first + i * 8;
             if (m < M && colok) {
-              f16* d = hb + (part == 0 ? (size_t)m : (size_t)(p.t_off + t) * p.arena_rows + (size_t)b * p.slot_stride) * hd + ch * 8;
+              f16* d = hb + (part == 0 ? (size_t)m : (size_t)(p.t_off + t) * p.arena_rows + (size_t)b * p.slot_stride) * hd + coff;
               *(f16x8*)d = v4[i];
             }
             t += 8;
